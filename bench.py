@@ -12,8 +12,17 @@ only collectives are the timing barrier and the max-over-ranks reduction, both
 over gloo on the host (the device is synchronised before each, so nothing on
 the path needs RCCL — north_star: "no RCCL collective").
 
-The same line carries `config5`: BASELINE config 5 (8 M x 9000 B, 75.5 GB)
-sharded over the N GPUs — strong scaling, its own timed region after the NS
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline
+needs: it fills the batch, warms up, times the K steps and prints the line
+(`value`, `ms_per_step`, the HIP-event `roofline`, `per_rank`); with
+`--dump-outputs DIR` it also writes the last timed step's checksums to
+DIR/checksums.npy (float32).  Everything described below that is more than
+that — `config5`, the digest checks (`bit_exact`), the PMC traffic pass,
+`cpu_baseline`, `host_inclusive` — is measured with `--full` only, and is
+null in a plain run's line.
+
+With `--full` the same line carries `config5`: BASELINE config 5
+(8 M x 9000 B, 75.5 GB) sharded over the N GPUs — strong scaling, its own timed region after the NS
 one — so a 1/2/4/8 run measures both the north-star weak-scaling value and the
 config-5 curve.
 
@@ -100,7 +109,18 @@ def parse():
                     help="skip the BASELINE config-5 strong-scaling sub-measurement")
     ap.add_argument("--config5-steps", type=int, default=0, help="timed steps of config 5 (0 = --steps)")
     ap.add_argument("--no-host", action="store_true", help="skip the host_inclusive sub-object")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the PMC traffic pass, the "
+                         "outputs against the reference digests, the CPU baseline, host_inclusive and config 5 "
+                         "(each still narrowed by its own --no-* / --cpu-seconds option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the checksums of the last timed step to "
+                         "DIR/checksums.npy (float32, one value per segment; rank r of an N > 1 run writes "
+                         "DIR/checksums_rank<r>.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------ rank launcher -
@@ -155,6 +175,19 @@ def gather_u16(out, dist):
     if parts is None:
         return None
     return np.frombuffer(b"".join(parts), dtype=np.uint16)
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: what the last timed step left in the caller's output
+    array — every segment's 16-bit checksum, as float32 (exact) — in
+    DIR/checksums.npy (rank r of an N > 1 run: DIR/checksums_rank<r>.npy;
+    4 bytes per segment, 32 MB for the largest workload's 8 M segments).  The
+    inputs are the workload's seeded spec stream, identical from run to run."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    name = "checksums.npy" if world == 1 else f"checksums_rank{rank}.npy"
+    np.save(os.path.join(path, name), u16_host(out).astype(np.float32))
 
 
 def gather_rows(row, dist):
@@ -426,7 +459,7 @@ def main():
 
     # the PMC child pass runs before this process touches the GPU
     traffic, traffic_src = (None, "skipped")
-    if not args.pmc_child and not args.no_pmc and rank == 0:
+    if args.full and not args.pmc_child and not args.no_pmc and rank == 0:
         # rank 0's launches (every rank runs the same per-GPU workload); at
         # N > 1 the other ranks wait in the group rendezvous meanwhile
         traffic, traffic_src = pmc_traffic(args)
@@ -518,9 +551,13 @@ def main():
     # r's shard of a weak-scaling workload is global segments [r n, (r+1) n)
     # of one spec stream, and the reference's outputs for each such slice
     # are hashed in configs.json (shard 0 = the BASELINE batch itself)
-    gold = golden_configs()
-    ns_sha = sha256_u16(u16_host(out))
-    key = GOLDEN_KEY.get(args.workload)
+    # (--full only: a plain run times the steps and, with --dump-outputs,
+    # writes their outputs; it hashes and compares nothing)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+    gold = golden_configs() if args.full else None
+    ns_sha = sha256_u16(u16_host(out)) if args.full else None
+    key = GOLDEN_KEY.get(args.workload) if args.full else None
     # this rank's shard digest: global segments [rank n, (rank+1) n) of the
     # workload's spec stream (weak scaling: n per rank at any N)
     want = None
@@ -534,7 +571,8 @@ def main():
                             "GiB_s": round(bytes_step * args.steps / own_s / 2**30, 2),
                             "roofline_frac": round(achieved / HBM_PEAK_GBS, 4), "out_sha256": ns_sha,
                             "bit_exact": None if want is None else ns_sha == want}, dist)
-    bit_exact, checked = None, "no reference digest for this workload"
+    bit_exact, checked = None, ("no reference digest for this workload" if args.full else
+                                "not checked (--full compares the outputs with the reference digests)")
     if key and scaling == "weak":
         if rank == 0:
             marks = [r["bit_exact"] for r in per_rank]
@@ -551,16 +589,16 @@ def main():
         checked = f"all ranks' {n_total} outputs vs tests/golden/configs.json[{key!r}].out_sha256"
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(data, init, out, seg, args.cpu_seconds, args.cpu_threads)
     host = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if args.full and rank == 0 and world == 1 and not args.no_host:
         host = host_inclusive(eng, data, init, out, n, seg)
     del data, init, out
 
     # BASELINE config 5: 8 M x 9000 B sharded over the N GPUs (strong scaling)
     config5 = None
-    if not args.no_config5 and args.workload != "jumbo_8Mx9000":
+    if args.full and not args.no_config5 and args.workload != "jumbo_8Mx9000":
         n5, seg5, seed5, _ = WORKLOADS["jumbo_8Mx9000"]
         sh5 = shard.fixed_stride_shard(n5, seg5, seg5, rank, world)
         torch.cuda.empty_cache()
@@ -604,6 +642,7 @@ def main():
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": scaling,
+            "full": args.full,
             "vs_baseline": None,
             "dtype": "u8",
             "data": "synthetic (seeded splitmix64 spec, DESIGN.md §Workload spec)",

@@ -65,6 +65,39 @@ def test_world_size_must_match_gpus():
     assert "WORLD_SIZE=2 but --gpus 1" in r.stderr
 
 
+def test_dump_outputs_writes_exact_float32(tmp_path):
+    """--dump-outputs: the int16 output tensor's 16-bit patterns as float32
+    values 0..65535, one file per rank of an N > 1 run"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    u16 = np.array([0, 1, 0x7FFF, 0x8000, 0xFFFF, 0x5A5A], dtype=np.uint16)
+    out = torch.from_numpy(u16.view(np.int16).copy())
+    bench.dump_outputs(str(tmp_path / "one"), out, 0, 1)
+    got = np.load(tmp_path / "one" / "checksums.npy")
+    assert got.dtype == np.float32 and (got == u16.astype(np.float32)).all()
+    bench.dump_outputs(str(tmp_path / "two"), out, 1, 2)
+    assert sorted(os.listdir(tmp_path / "two")) == ["checksums_rank1.npy"]
+
+
+def test_full_is_off_by_default(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_cpu_share_reports_usable_cpus():
     sys.path.insert(0, ROOT)
     import bench

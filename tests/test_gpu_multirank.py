@@ -74,7 +74,7 @@ def test_bench_two_ranks_one_line():
     JSON line — gloo's connection messages kept off it — carrying the NS
     weak-scaling value over 2 x 1 M segments and the config-5 strong-scaling
     view (8 M x 9000 B, 4 M segments per rank)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1",
                         "--settle-ms", "10", "--config5-steps", "2", "--no-pmc", "--cpu-seconds", "0"],
                        capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
