@@ -6,7 +6,7 @@
 // reference's own util/tools headers when integrated.
 //
 // Byte map of one TCP-in-IPv4 datagram as the device kernels see it
-// (k_ipv4_tcp, csrc/kernels/icsum_kernels.hip), with the member that owns
+// (k_ipv4_tcp, csrc/kernels/icsum_ipv4.h), with the member that owns
 // each field:
 //
 //   IPv4 [0,20)   IPv4Header                     (ipv4_header.h)

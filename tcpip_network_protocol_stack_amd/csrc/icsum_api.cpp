@@ -3,7 +3,7 @@
 // Thin, exception-free layer: argument validation, device binding, error
 // strings, and the extern "C" entry points.  Which kernel runs a batch is
 // icsum_dispatch.cpp's business, the host-memory pipeline icsum_host.cpp's;
-// all arithmetic happens in the HIP kernels (kernels/icsum_kernels.hip) and
+// all arithmetic happens in the HIP kernels (kernels/icsum_kernels.hip and its family headers) and
 // there is no CPU fallback — without a usable GPU every call returns an error.
 #include <algorithm>
 #include <cstdarg>

@@ -2,7 +2,7 @@
 // which kernel and geometry runs a batch, the plan cache that remembers the
 // device's view of an offsets batch's length mix, the binned launches, the
 // device wrap's one- or two-pass choice and the multi-batch grouping.  All
-// arithmetic happens in the HIP kernels (kernels/icsum_kernels.hip).
+// arithmetic happens in the HIP kernels (kernels/icsum_kernels.hip and its family headers).
 #include <algorithm>
 #include <string>
 #include <vector>

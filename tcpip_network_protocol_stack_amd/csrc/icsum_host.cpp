@@ -205,7 +205,7 @@ void host_patch_fields(uint8_t* bytes, const uint64_t* offsets, uint64_t stride,
 }
 
 // Wait for a zero-copy chunk: spin on its completion word (written by the
-// launch's last block, icsum_kernels.hip signal_done) for
+// launch's last block, kernels/icsum_common.h signal_done) for
 // up to a millisecond — a zero-copy chunk is at most zero_copy_max bytes, tens
 // of microseconds over PCIe — then block on the slot's stream, which also
 // surfaces a kernel fault as a HIP error instead of a hang.  A launch that

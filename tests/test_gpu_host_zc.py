@@ -141,7 +141,7 @@ def test_zc_path_taken_per_threshold(zeng, orc, request):
 
 def test_zc_completion_over_many_blocks_and_two_pass_wrap(orc):
     """The completion word comes from the launch's last block (a block-count
-    ticket, icsum_kernels.hip signal_done): zero-copy launches of hundreds of
+    ticket, kernels/icsum_common.h signal_done): zero-copy launches of hundreds of
     blocks, back to back on every slot (the ticket word must be back at 0
     after each), and the two-pass wrap, whose header pass completes the call."""
     from conftest import engine_with

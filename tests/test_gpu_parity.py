@@ -15,7 +15,7 @@ from helpers import kat_cases, pack_contiguous, wires
 pytestmark = pytest.mark.gpu
 
 # every instantiated (LPS, UNROLL, MODE) of k_checksum the dispatch can reach —
-# keep in sync with ICS_GEOMETRIES in icsum_kernels.hip (MODE 2: 16-byte grid
+# keep in sync with ICS_GEOMETRIES in kernels/icsum_common.h (MODE 2: 16-byte grid
 # fully masked, 3: 128-byte-line grid with primed boundary loads) — plus MODE
 # 4, k_checksum_tiny (one lane per segment)
 GEOMETRIES = [(4, 1, 2), (4, 2, 2), (8, 2, 2), (8, 8, 3), (16, 4, 3), (16, 5, 3), (16, 6, 3), (16, 7, 3), (16, 8, 3),
