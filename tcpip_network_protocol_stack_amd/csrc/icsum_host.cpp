@@ -117,9 +117,10 @@ int next_chunk(const ics_ctx* ctx, const uint64_t* offsets, uint64_t stride, uin
     return ICS_OK;
   }
   if (!offsets) {
-    const uint64_t per = std::max<uint64_t>(stride, seg_len);
-    uint64_t k = per ? cap_b / per : cap_n;
-    if (k == 0) k = 1;  // stride > slot but the segment itself fits
+    // k segments take (k - 1) * stride + seg_len bytes (seg_len <= cap_b here):
+    // the padding behind the last one is not staged, overlapping segments
+    // (stride < seg_len) share their bytes, and stride 0 is one segment's bytes
+    uint64_t k = stride ? (cap_b - seg_len) / stride + 1 : cap_n;
     k = std::min<uint64_t>({k, cap_n, n - i0});
     *c = {i0, i0 + k, i0 * stride, (i0 + k - 1) * stride + seg_len};
     return ICS_OK;

@@ -200,9 +200,11 @@ class Engine:
                                                   _stream(stream, self.device)))
         return hdrs
 
-    def tcp_wrap_headers_host(self, payloads, msgs, n, offsets=None, stride=0, payload_len=0):
+    def tcp_wrap_headers_host(self, payloads, msgs, n, offsets=None, stride=0, payload_len=0, hdrs=None):
+        """Payload-only batch in host memory; the 40 header bytes of datagram i
+        go to hdrs[40 i:] (a numpy uint8 array, allocated when absent)."""
         msgs = np.ascontiguousarray(msgs, dtype=TCP_MSG_DTYPE)
-        hdrs = np.empty(n * 40, dtype=np.uint8)
+        hdrs = np.empty(n * 40, dtype=np.uint8) if hdrs is None else hdrs
         self._check(self.lib.ics_tcp_wrap_headers_host(self.ctx, _ptr(payloads), _ptr(offsets), stride, payload_len,
                                                        n, msgs.ctypes.data, hdrs.ctypes.data))
         return hdrs
@@ -235,16 +237,18 @@ class Engine:
         return hdrs, status
 
     # ---- host-memory (PCIe-inclusive) variants -----------------------------
-    def checksum_batch_host(self, data, n, offsets=None, stride=0, seg_len=0, init=None):
-        out = np.empty(n, dtype=np.uint16)
+    def checksum_batch_host(self, data, n, offsets=None, stride=0, seg_len=0, init=None, out=None):
+        """Host-memory outputs (numpy, at least n elements) are allocated when absent."""
+        out = np.empty(n, dtype=np.uint16) if out is None else out
         self._check(self.lib.ics_checksum_batch_host(self.ctx, _ptr(data), _ptr(offsets), stride, seg_len,
                                                _ptr(init), _ptr(out), n))
         return out
 
-    def ipv4_tcp_batch_host(self, dgrams, n, mode, offsets=None, stride=0, dgram_len=0):
-        ip = np.empty(n, dtype=np.uint16)
-        tcp = np.empty(n, dtype=np.uint16)
-        st = np.empty(n, dtype=np.uint8)
+    def ipv4_tcp_batch_host(self, dgrams, n, mode, offsets=None, stride=0, dgram_len=0, ip_ck=None, tcp_ck=None,
+                            status=None):
+        ip = np.empty(n, dtype=np.uint16) if ip_ck is None else ip_ck
+        tcp = np.empty(n, dtype=np.uint16) if tcp_ck is None else tcp_ck
+        st = np.empty(n, dtype=np.uint8) if status is None else status
         self._check(self.lib.ics_ipv4_tcp_batch_host(self.ctx, _ptr(dgrams), _ptr(offsets), stride, dgram_len,
                                                n, mode, _ptr(ip), _ptr(tcp), _ptr(st)))
         return ip, tcp, st
