@@ -175,6 +175,84 @@ int ics_router_ttl_headers(ics_ctx* ctx, const void* d_dgrams, const uint64_t* d
                            uint64_t stride, uint64_t dgram_len, uint64_t n, void* d_hdrs,
                            uint8_t* d_status, void* stream);
 
+/* ---- route lookup (src/router/router.cpp:15-24 add_route, :77-87 match) -- */
+/* A route table with Router::match's exact semantics.  The table functions
+ * need no context and no GPU.  add(prefix, L, ...) stores the route under
+ * (L, rotr(prefix, 32 - L)), a later add with the same (L, prefix) replacing
+ * the earlier one; match(addr) tries L = 31 down to 0 with addr >> (32 - L)
+ * and the first hit wins.  What follows from that is reproduced bit for bit:
+ *   - a route whose prefix has a bit set below its top L bits (L = 0: any bit)
+ *     is accepted and can never match ("dead");
+ *   - bit 0 of the address never takes part (the longest length tried is 31);
+ *   - the answer's next hop is next_hop.value_or(dst): the address looked up
+ *     for a direct route, and a present next hop of 0.0.0.0 is NOT direct.
+ * The one deliberate difference: prefix_len 32 indexes past the reference's
+ * 32-entry array (undefined behaviour there); here prefix_len > 31 is
+ * ICS_ERR_INVALID.  iface is the reference's interface_num and must be below
+ * 2^31.  A table is guarded by a mutex (concurrent matches are allowed) and
+ * is compiled, on the first match or device use after a change, into the
+ * flat 16-8-7 trie the device reads; ICS_ERR_NOMEM if that
+ * image would reach 2^31 words.  A table belongs to the library that created
+ * it (libicsum.so or libicsum_debug.so). */
+typedef struct ics_route_table ics_route_table;
+typedef struct ics_route_stats_t {
+  uint64_t routes_added;  /* adds since create / clear */
+  uint64_t routes_live;   /* ... of them, those whose prefix can match */
+  uint64_t routes_dead;   /* ... and those that never can */
+  uint64_t route_records; /* distinct live (prefix_len, prefix): the image's route records */
+  uint64_t image_words;   /* trie words: 65536 + 256 l2_chunks + 128 l3_chunks */
+  uint64_t l2_chunks;     /* 256-word chunks (routes longer than /16 under a /16) */
+  uint64_t l3_chunks;     /* 128-word chunks (routes longer than /24 under a /24) */
+} ics_route_stats_t;
+int ics_route_table_create(ics_route_table** out);
+int ics_route_table_destroy(ics_route_table* tbl);
+int ics_route_table_add(ics_route_table* tbl, uint32_t prefix, uint32_t prefix_len, uint32_t iface,
+                        int has_next_hop, uint32_t next_hop);
+int ics_route_table_clear(ics_route_table* tbl);
+/* 1: matched (*iface, *next_hop set; either may be NULL), 0: no route
+ * (*iface = 0xFFFFFFFF, *next_hop = 0), negative: error.  Walks the same
+ * compiled image the device reads. */
+int ics_route_table_match(ics_route_table* tbl, uint32_t addr, uint32_t* iface, uint32_t* next_hop);
+int ics_route_table_stats(ics_route_table* tbl, ics_route_stats_t* stats);
+
+/* d_iface[i], d_next_hop[i] = match(d_addrs[i]) for n host-order addresses,
+ * one lane each (k_route_lookup); no route: 0xFFFFFFFF and 0.  Either output
+ * may be NULL.
+ * Device image (all three calls below): the context keeps the images of a few
+ * tables (least recently used replaced) and uploads a table's image on
+ * `stream` on its first use after a change; that upload synchronises
+ * `stream`, every other call only enqueues.  Calls on one stream see table
+ * changes in order; changing a table while a launch on ANOTHER stream still
+ * uses it is the caller's race. */
+#define ICS_NO_ROUTE 0xFFFFFFFFu
+int ics_route_lookup_batch(ics_ctx* ctx, ics_route_table* tbl, const uint32_t* d_addrs, uint64_t n,
+                           uint32_t* d_iface, uint32_t* d_next_hop, void* stream);
+
+/* Router::route whole (router.cpp:27-70): ics_router_ttl_batch's step, then
+ * match(header.dst) for every datagram that forwards — the ttl decrement and
+ * checksum recompute come first, so a datagram with no route has been
+ * rewritten (and is then dropped by the caller).  d_status[i] bits:
+ * ICS_RT_FORWARD is ics_router_ttl_batch's status 1, and the bytes written
+ * are exactly that call's, route or no route; ICS_RT_ROUTED: forwarded and a
+ * route matched, d_iface[i] / d_next_hop[i] = the egress interface and
+ * next_hop.value_or(dst).  Without ROUTED they are 0xFFFFFFFF and 0.
+ * d_iface / d_next_hop may be NULL independently.  The lookup runs inside the
+ * router kernel, on the dst it already holds: prefer these calls to the bare
+ * step followed by ics_route_lookup_batch (1 M x 1500 B, headers apart: 41-51
+ * us fused against 45-63 us as two launches and 33-34 us for the bare step,
+ * from a 264 KiB to a 42 MB image). */
+#define ICS_RT_FORWARD 0x01u
+#define ICS_RT_ROUTED 0x02u
+int ics_router_route_batch(ics_ctx* ctx, ics_route_table* tbl, void* d_dgrams, const uint64_t* d_offsets,
+                           uint64_t stride, uint64_t dgram_len, uint64_t n, uint8_t* d_status,
+                           uint32_t* d_iface, uint32_t* d_next_hop, void* stream);
+/* The same with the forwarded headers apart, as ics_router_ttl_headers:
+ * d_hdrs and (d_status & ICS_RT_FORWARD) are exactly that call's. */
+int ics_router_route_headers(ics_ctx* ctx, ics_route_table* tbl, const void* d_dgrams,
+                             const uint64_t* d_offsets, uint64_t stride, uint64_t dgram_len, uint64_t n,
+                             void* d_hdrs, uint8_t* d_status, uint32_t* d_iface, uint32_t* d_next_hop,
+                             void* stream);
+
 /* ---- a14 / §8(f) rank 2: device-side wrap_tcp_in_ip -------------------- */
 /* The fields of one TCPMessage as TCPOverIPv4Adapter::wrap_tcp_in_ip
  * (util/tcp_over_ip/tcp_over_ip.cpp:69-88) puts them on the wire.  28 bytes. */
@@ -330,6 +408,9 @@ int ics_stream_synchronize(ics_ctx* ctx, void* stream);
 #define ICS_K_ROUTER_HDRS 14     /* k_router_hdrs: the router step, forwarded headers apart */
 #define ICS_K_TICK 15            /* k_tick: a zero-copy *_host tick of <= 16 offsets segments, offsets in the kernel arguments */
 #define ICS_K_TICK_SERVER 16     /* the resident tick server took the tick (ics_set_tick_server) */
+#define ICS_K_ROUTE_LOOKUP 17    /* k_route_lookup: one lane per address */
+#define ICS_K_ROUTER_ROUTE 18    /* k_router_ttl with the route lookup fused */
+#define ICS_K_ROUTER_ROUTE_HDRS 19 /* k_router_hdrs with the route lookup fused */
 /* last_lps / last_unroll by kernel:
  *   ICS_K_CHECKSUM .. ICS_K_WRAP_2PASS  lanes per segment / loads in flight per lane
  *   ICS_K_TWOCLASS, ICS_K_IPV4_TWOCLASS  long-segment lanes (16) / segments per wave (16 or 32; 8 only under ICSUM_FORCE twoclass=8)
@@ -338,6 +419,7 @@ int ics_stream_synchronize(ics_ctx* ctx, void* stream);
  *                 call, clamp(20 KiB / mean segment length, 1, 63) from the
  *                 cached plan (ICSUM_FORCE span_segs pins it)
  *   ICS_K_ROUTER, ICS_K_ROUTER_HDRS  0 / 0
+ *   ICS_K_ROUTE_LOOKUP, ICS_K_ROUTER_ROUTE, ICS_K_ROUTER_ROUTE_HDRS  0 / 0
  *   ICS_K_TICK, ICS_K_TICK_SERVER  16 / 8 (a 16-lane group per segment, one block) */
 #define ICS_BV_DENSE64 0 /* fixed stride == length == 64 B, 16-byte aligned */
 #define ICS_BV_TINY 1    /* one lane per segment (ACK-sized fixed lengths) */

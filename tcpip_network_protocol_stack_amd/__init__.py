@@ -6,14 +6,14 @@ package is the binding used by tests/ and bench.py.
 """
 from ._lib import LIB_PATH, IcsumError, load  # noqa: F401
 
-__all__ = ["LIB_PATH", "IcsumError", "load", "Engine"]
+__all__ = ["LIB_PATH", "IcsumError", "load", "Engine", "RouteTable"]
 
 
 def __getattr__(name):
     # torch is imported lazily so that `import tcpip_network_protocol_stack_amd`
     # stays cheap for the C-ABI-only users (symbol checks, FFI stubs)
-    if name in ("Engine", "engine"):
+    if name in ("Engine", "RouteTable", "engine"):
         from . import engine
 
-        return engine.Engine if name == "Engine" else engine
+        return engine if name == "engine" else getattr(engine, name)
     raise AttributeError(name)

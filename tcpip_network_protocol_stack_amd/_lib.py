@@ -56,14 +56,25 @@ class DgramBatch(ctypes.Structure):
                 ("tcp_ck", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class RouteStats(ctypes.Structure):
+    """struct ics_route_stats_t (include/icsum.h)."""
+    _fields_ = [("routes_added", ctypes.c_uint64), ("routes_live", ctypes.c_uint64),
+                ("routes_dead", ctypes.c_uint64), ("route_records", ctypes.c_uint64),
+                ("image_words", ctypes.c_uint64), ("l2_chunks", ctypes.c_uint64), ("l3_chunks", ctypes.c_uint64)]
+
+
 # ICS_K_* kernel ids of ics_dispatch_info_t.last_kernel
 KERNELS = {1: "checksum", 2: "small", 3: "tiny", 4: "dense", 5: "twoclass", 6: "binned", 7: "ipv4",
            8: "ipv4_twoclass", 9: "wrap", 10: "wrap_2pass", 11: "router", 12: "batchv", 13: "tile",
-           14: "router_hdrs", 15: "tick", 16: "tick_server"}
+           14: "router_hdrs", 15: "tick", 16: "tick_server", 17: "route_lookup", 18: "router_route",
+           19: "router_route_hdrs"}
+ICS_RT_FORWARD, ICS_RT_ROUTED = 0x01, 0x02
+ICS_NO_ROUTE = 0xFFFFFFFF
 
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _int = ctypes.c_int
+_u32 = ctypes.c_uint32
 
 # name -> (restype, argtypes); every symbol include/icsum.h and
 # include/icsum_workload.h declare
@@ -84,6 +95,15 @@ SIGNATURES = {
     "ics_ipv4_tcp_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _int, _p, _p, _p, _p]),
     "ics_router_ttl_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p]),
     "ics_router_ttl_headers": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p]),
+    "ics_route_table_create": (_int, [ctypes.POINTER(_p)]),
+    "ics_route_table_destroy": (_int, [_p]),
+    "ics_route_table_add": (_int, [_p, _u32, _u32, _u32, _int, _u32]),
+    "ics_route_table_clear": (_int, [_p]),
+    "ics_route_table_match": (_int, [_p, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "ics_route_table_stats": (_int, [_p, ctypes.POINTER(RouteStats)]),
+    "ics_route_lookup_batch": (_int, [_p, _p, _p, _u64, _p, _p, _p]),
+    "ics_router_route_batch": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
+    "ics_router_route_headers": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
     "ics_tcp_wrap_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "ics_tcp_wrap_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p]),
     "ics_tcp_wrap_headers": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p, _p]),

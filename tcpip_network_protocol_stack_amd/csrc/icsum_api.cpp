@@ -52,9 +52,11 @@ int bounds_verdict(hipStream_t st, int rc) {
   ICS_HIP(icsum::bounds_take(st, &flags, &what));
   if (flags)
     return fail(ICS_ERR_INVALID,
-                "bounds check: %s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
+                "bounds check: %s%s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
                 (flags & 2u) ? "offsets not monotone " : "", (flags & 4u) ? "header load past a datagram " : "",
-                (flags & 2u) && !(flags & 5u) ? "segment" : "address", (unsigned long long)what);
+                (flags & 8u) ? "route image index outside the image " : "",
+                (flags & 2u) && !(flags & 13u) ? "segment" : (flags & 8u) && !(flags & 7u) ? "image word" : "address",
+                (unsigned long long)what);
   return ICS_OK;
 }
 
@@ -134,6 +136,7 @@ int ics_destroy(ics_ctx* ctx) {
   if (!ctx) return ICS_OK;
   if (bind(ctx) == ICS_OK) {
     free_staging(ctx);
+    free_routes(ctx);
     if (ctx->d_zero) (void)hipFree(ctx->d_zero);
     if (ctx->plan_host) (void)hipHostFree(ctx->plan_host);
     ctx->scratch.release();
@@ -318,6 +321,49 @@ int ics_router_ttl_headers(ics_ctx* ctx, const void* d_dgrams, const uint64_t* d
   return bounds_verdict(static_cast<hipStream_t>(stream),
                         router_device(ctx, sp, static_cast<uint32_t*>(d_hdrs), d_status,
                                       static_cast<hipStream_t>(stream)));
+}
+
+int ics_route_lookup_batch(ics_ctx* ctx, ics_route_table* tbl, const uint32_t* d_addrs, uint64_t n,
+                           uint32_t* d_iface, uint32_t* d_next_hop, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (!tbl) return fail(ICS_ERR_INVALID, "null route table");
+  if (n == 0) return ICS_OK;
+  if (!d_addrs) return fail(ICS_ERR_INVALID, "null device buffer");
+  if ((reinterpret_cast<uintptr_t>(d_addrs) | reinterpret_cast<uintptr_t>(d_iface) |
+       reinterpret_cast<uintptr_t>(d_next_hop)) & 3u)
+    return fail(ICS_ERR_INVALID, "address / interface / next-hop arrays not 4-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, route_device(ctx, tbl, nullptr, d_addrs, n, nullptr, nullptr, d_iface, d_next_hop, st));
+}
+
+int ics_router_route_batch(ics_ctx* ctx, ics_route_table* tbl, void* d_dgrams, const uint64_t* d_offsets,
+                           uint64_t stride, uint64_t dgram_len, uint64_t n, uint8_t* d_status, uint32_t* d_iface,
+                           uint32_t* d_next_hop, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (!tbl) return fail(ICS_ERR_INVALID, "null route table");
+  if (n == 0) return ICS_OK;
+  if (!d_dgrams || !d_status) return fail(ICS_ERR_INVALID, "null device buffer");
+  if ((reinterpret_cast<uintptr_t>(d_iface) | reinterpret_cast<uintptr_t>(d_next_hop)) & 3u)
+    return fail(ICS_ERR_INVALID, "interface / next-hop arrays not 4-byte aligned");
+  const icsum::SegSpec sp{static_cast<const uint8_t*>(d_dgrams), d_offsets, stride, dgram_len, n, ctx->d_zero};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, route_device(ctx, tbl, &sp, nullptr, n, nullptr, d_status, d_iface, d_next_hop, st));
+}
+
+int ics_router_route_headers(ics_ctx* ctx, ics_route_table* tbl, const void* d_dgrams, const uint64_t* d_offsets,
+                             uint64_t stride, uint64_t dgram_len, uint64_t n, void* d_hdrs, uint8_t* d_status,
+                             uint32_t* d_iface, uint32_t* d_next_hop, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (!tbl) return fail(ICS_ERR_INVALID, "null route table");
+  if (n == 0) return ICS_OK;
+  if (!d_dgrams || !d_hdrs || !d_status) return fail(ICS_ERR_INVALID, "null device buffer");
+  if (reinterpret_cast<uintptr_t>(d_hdrs) & 3u) return fail(ICS_ERR_INVALID, "header array not 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_iface) | reinterpret_cast<uintptr_t>(d_next_hop)) & 3u)
+    return fail(ICS_ERR_INVALID, "interface / next-hop arrays not 4-byte aligned");
+  const icsum::SegSpec sp{static_cast<const uint8_t*>(d_dgrams), d_offsets, stride, dgram_len, n, ctx->d_zero};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, route_device(ctx, tbl, &sp, nullptr, n, static_cast<uint32_t*>(d_hdrs), d_status, d_iface,
+                                         d_next_hop, st));
 }
 
 int ics_checksum_batch_host(ics_ctx* ctx, const void* h_bytes, const uint64_t* h_offsets,

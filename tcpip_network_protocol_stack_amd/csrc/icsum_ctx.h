@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <memory>
 #include <mutex>
+#include <vector>
 
 #include "icsum.h"
 #include "common/par_for.h"
@@ -233,6 +234,30 @@ struct ics_ctx {
   bool srv_launched = false;  // a server was launched (its `state` words say whether it still runs)
   uint64_t n_srv_jobs = 0, n_srv_launches = 0;
   uint32_t srv_pollers = 1;  // waves polling the mailbox, staggered (ICSUM_FORCE srv_pollers, 1..4)
+  // route images (ics_route_lookup_batch, ics_router_route_*): the compiled
+  // images of up to kRouteSlots tables, keyed by the table's id and generation
+  // (never by pointer: a destroyed table's address is reused), the least
+  // recently used slot replaced.  A slot's image is uploaded on the call's
+  // stream when the generation differs (the upload waits for the slot's last
+  // launch and synchronises the stream).  Buffers only grow, by doubling; an
+  // outgrown one is kept until ics_destroy (hipFree synchronises the whole
+  // device).  route_mu is held from the slot lookup through the
+  // launch, so no other thread replaces the slot in between.
+  static constexpr int kRouteSlots = 4;
+  struct RouteSlot {
+    uint64_t id = 0, gen = 0;  // id 0: empty
+    uint32_t* d = nullptr;
+    size_t cap = 0;  // bytes
+    uint64_t nwords = 0;
+    uint32_t nrecs = 0;
+    uint64_t used = 0;        // LRU clock
+    hipEvent_t ev = nullptr;  // recorded behind the last launch that read the slot
+    bool launched = false;
+  };
+  RouteSlot route_slot[kRouteSlots];
+  uint64_t route_clock = 0;
+  std::vector<void*> route_retired;
+  std::mutex route_mu;
 };
 
 namespace icsum::detail {
@@ -311,6 +336,13 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
 // c2: the router's TTL decrement + header checksum recompute, in place
 // (d_hdrs null) or with the forwarded headers to d_hdrs (20 bytes each).
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st);
+// Router::match on the device: sp null = the lookup-only batch over d_addrs
+// (n addresses), else the router step of `sp` with the lookup fused (d_hdrs
+// as router_device).  Brings the table's image up to date on `st` first.
+int route_device(ics_ctx* ctx, ics_route_table* tbl, const icsum::SegSpec* sp, const uint32_t* d_addrs, uint64_t n,
+                 uint32_t* d_hdrs, uint8_t* d_status, uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st);
+// Release the route images (ics_destroy).
+void free_routes(ics_ctx* ctx);
 // Multi-batch calls: batches grouped by kernel shape, one launch per group.
 int checksum_batchv_device(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, hipStream_t st);
 int ipv4_batchv_device(ics_ctx* ctx, const ics_dgram_batch* batches, uint32_t k, int mode, hipStream_t st);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "icsum_ctx.h"
+#include "icsum_route.h"
 
 namespace icsum::detail {
 
@@ -497,6 +498,81 @@ int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint
     note(ctx, ICS_K_ROUTER);
   }
   return ICS_OK;
+}
+
+namespace {
+// the table stays locked (its image valid) until the image is on the device
+struct RouteImageLock {
+  ics_route_table* tbl = nullptr;
+  ~RouteImageLock() {
+    if (tbl) route_image_release(tbl);
+  }
+};
+}  // namespace
+
+int route_device(ics_ctx* ctx, ics_route_table* tbl, const icsum::SegSpec* sp, const uint32_t* d_addrs, uint64_t n,
+                 uint32_t* d_hdrs, uint8_t* d_status, uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st) {
+  std::lock_guard<std::mutex> lock(ctx->route_mu);
+  ics_ctx::RouteSlot* slot = nullptr;
+  {
+    RouteImageView v;
+    if (int rc = route_image_acquire(tbl, &v)) return rc;
+    RouteImageLock held{tbl};
+    for (auto& s : ctx->route_slot)
+      if (s.id == v.id) slot = &s;
+    if (!slot) {  // the least recently used (an empty slot first)
+      slot = &ctx->route_slot[0];
+      for (auto& s : ctx->route_slot)
+        if (s.used < slot->used) slot = &s;
+    }
+    if (slot->id != v.id || slot->gen != v.gen) {
+      slot->id = 0;  // not trusted until the upload has landed
+      if (slot->launched) ICS_HIP(hipEventSynchronize(slot->ev));  // a launch on another stream may still read it
+      const size_t need = (size_t(v.nwords) + 2 * size_t(v.nrecs)) * 4;
+      if (need > slot->cap) {
+        const size_t cap = (std::max(need, 2 * slot->cap) + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
+        void* p = nullptr;
+        ICS_HIP(hipMalloc(&p, cap));
+        if (slot->d) ctx->route_retired.push_back(slot->d);
+        slot->d = static_cast<uint32_t*>(p);
+        slot->cap = cap;
+      }
+      ICS_HIP(hipMemcpyAsync(slot->d, v.words, need, hipMemcpyHostToDevice, st));
+      ICS_HIP(hipStreamSynchronize(st));  // the table's host image is released below
+      slot->id = v.id;
+      slot->gen = v.gen;
+      slot->nwords = v.nwords;
+      slot->nrecs = v.nrecs;
+    }
+  }
+  slot->used = ++ctx->route_clock;
+  if (!slot->ev) ICS_HIP(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
+  const icsum::RouteImg img{slot->d, slot->nwords, slot->nrecs};
+  if (!sp) {
+    ICS_HIP(icsum::launch_route_lookup(d_addrs, n, img, d_iface, d_next_hop, st));
+    note(ctx, ICS_K_ROUTE_LOOKUP);
+  } else {
+    ICS_HIP(icsum::launch_router_route(*sp, img, d_hdrs, d_status, d_iface, d_next_hop, st));
+    note(ctx, d_hdrs ? ICS_K_ROUTER_ROUTE_HDRS : ICS_K_ROUTER_ROUTE);
+  }
+  if (hipEventRecord(slot->ev, st) == hipSuccess) {
+    slot->launched = true;
+  } else {  // cannot track this launch: nothing may replace the image under it
+    (void)hipStreamSynchronize(st);
+    slot->launched = false;
+  }
+  return ICS_OK;
+}
+
+void free_routes(ics_ctx* ctx) {
+  for (auto& s : ctx->route_slot) {
+    if (s.launched) (void)hipEventSynchronize(s.ev);
+    if (s.d) (void)hipFree(s.d);
+    if (s.ev) (void)hipEventDestroy(s.ev);
+    s = {};
+  }
+  for (void* p : ctx->route_retired) (void)hipFree(p);
+  ctx->route_retired.clear();
 }
 
 namespace {

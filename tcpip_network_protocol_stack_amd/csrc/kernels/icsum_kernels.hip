@@ -24,7 +24,8 @@
 //   icsum_batchv.h      k_checksum_batchv, k_ipv4_batchv
 //   icsum_wrap.h        k_tcp_wrap, k_tcp_hdr
 //   icsum_tick.h        k_tick, k_tick_server
-//   icsum_router.h      k_router_ttl, k_router_hdrs
+//   icsum_route.h       the route image walk (Router::match), k_route_lookup
+//   icsum_router.h      k_router_ttl, k_router_hdrs (<true>: the route lookup fused)
 //   icsum_span.h        k_span (tile launches)
 //   icsum_generators.h  the workload generators
 // (icsum_device.h: arithmetic primitives; icsum_launch.h: the launchers' interface)
@@ -35,6 +36,7 @@
 #include "icsum_batchv.h"
 #include "icsum_wrap.h"
 #include "icsum_tick.h"
+#include "icsum_route.h"
 #include "icsum_router.h"
 #include "icsum_span.h"
 #include "icsum_generators.h"

@@ -179,6 +179,24 @@ hipError_t launch_router_ttl(const SegSpec& sp, uint8_t* status, hipStream_t st)
 // the datagrams read only (k_router_hdrs)
 hipError_t launch_router_hdrs(const SegSpec& sp, uint32_t* hdr_out, uint8_t* status, hipStream_t st);
 
+// Route lookup (Router::match, kernels/icsum_route.h).  A table's compiled
+// image in device memory (csrc/icsum_route.h has the layout): nwords trie
+// words, then two words per route record, 8-byte aligned.
+struct RouteImg {
+  const uint32_t* words;
+  uint64_t nwords;  // even
+  uint32_t nrecs;
+};
+// iface[i], next_hop[i] = match(addrs[i]); either output may be null
+hipError_t launch_route_lookup(const uint32_t* addrs, uint64_t n, const RouteImg& t, uint32_t* iface,
+                               uint32_t* next_hop, hipStream_t st);
+// the router step with match(dst) fused for the datagrams that forward:
+// status bit 0 as launch_router_ttl / launch_router_hdrs, bit 1 = a route
+// matched; iface / next_hop nullable.  In place (hdr_out null) or with the
+// forwarded headers to hdr_out.
+hipError_t launch_router_route(const SegSpec& sp, const RouteImg& t, uint32_t* hdr_out, uint8_t* status,
+                               uint32_t* iface, uint32_t* next_hop, hipStream_t st);
+
 // Tile launches of offsets batches (k_span): one wave per S (1..63)
 // consecutive segments, the span's bytes streamed whole in 4 KiB windows
 // whatever the lengths.  Checksum (out_kind as launch_checksum), the fused IPv4/TCP kernel

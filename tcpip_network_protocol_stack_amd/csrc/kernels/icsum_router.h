@@ -3,6 +3,7 @@
 #pragma once
 
 #include "icsum_ipv4.h"
+#include "icsum_route.h"
 
 namespace icsum {
 namespace {
@@ -16,11 +17,19 @@ namespace {
 // (git 7692616:tools/probe/router_probe.hip, profiles/r2_router_probe.jsonl): 1 M x 1500 B
 // 59.8 -> 57.3 us; the read-only floor of the same headers is 35-41 us, the
 // rest is the scattered 8-byte write-back of every forwarded header.
+// kRoute: Router::route's second half fused (router.cpp:53-66): a datagram
+// that forwards looks its dst (already in registers) up in the route image —
+// after the rewrite, as the reference matches after compute_checksum() —
+// status gains bit 1 on a match, and iface / next_hop (nullable) receive the
+// answer or the no-route values.  <false> is the bare step, unchanged.
+template <bool kRoute>
 __global__ __launch_bounds__(kBlock) void k_router_ttl(uint8_t* __restrict__ dg,
                                                        const uint64_t* __restrict__ offsets,
                                                        uint64_t stride, uint64_t dlen, uint64_t n,
                                                        uint8_t* __restrict__ status,
-                                                       const uint32_t* __restrict__ zpad) {
+                                                       const uint32_t* __restrict__ zpad, RouteImg rt,
+                                                       uint32_t* __restrict__ rt_iface,
+                                                       uint32_t* __restrict__ rt_hop) {
   constexpr uint32_t kG = kBlock / 2;
   const uint32_t lane = threadIdx.x & 1u;
   const uint64_t step = uint64_t(gridDim.x) * kG;
@@ -54,6 +63,7 @@ __global__ __launch_bounds__(kBlock) void k_router_ttl(uint8_t* __restrict__ dg,
     for (int w = 0; w < 6; ++w) d[w] = uint32_t(__shfl(int(mine[w / 2]), pair + (w & 1), 64));
     if (valid && lane == 0) {
       uint8_t st = 0;
+      [[maybe_unused]] uint32_t r_if = kNoRoute, r_hop = 0u;
       if (hdr) {
         Hdr h;
 #pragma unroll
@@ -80,9 +90,16 @@ __global__ __launch_bounds__(kBlock) void k_router_ttl(uint8_t* __restrict__ dg,
             store_be16(p + 10, c);
           }
           st = 1;
+          if constexpr (kRoute) {
+            if (route_find(rt, __builtin_bswap32(h.w[4]), r_if, r_hop)) st = 3;
+          }
         }
       }
       status[i] = st;
+      if constexpr (kRoute) {
+        if (rt_iface) rt_iface[i] = r_if;
+        if (rt_hop) rt_hop[i] = r_hop;
+      }
     }
   }
 }
@@ -99,11 +116,15 @@ __global__ __launch_bounds__(kBlock) void k_router_ttl(uint8_t* __restrict__ dg,
 // dropped or unparseable one gets 20 zero bytes.  Headers are read as in
 // k_router_ttl (two lanes per datagram, three dwords each); each wave stages
 // its 32 headers in LDS and stores them as 160 consecutive dwords.
+// kRoute: as k_router_ttl<true>; lane 0 of a forwarding pair walks the trie.
+template <bool kRoute>
 __global__ __launch_bounds__(kBlock) void k_router_hdrs(const uint8_t* __restrict__ dg,
                                                         const uint64_t* __restrict__ offsets, uint64_t stride,
                                                         uint64_t dlen, uint64_t n, uint32_t* __restrict__ hdr_out,
                                                         uint8_t* __restrict__ status,
-                                                        const uint32_t* __restrict__ zpad) {
+                                                        const uint32_t* __restrict__ zpad, RouteImg rt,
+                                                        uint32_t* __restrict__ rt_iface,
+                                                        uint32_t* __restrict__ rt_hop) {
   constexpr uint32_t kG = kBlock / 2, kPerWave = 32;
   __shared__ uint32_t stage[kBlock / 64][kPerWave * 5];
   const uint32_t lane = threadIdx.x & 1u, lane64 = threadIdx.x & 63u;
@@ -151,7 +172,17 @@ __global__ __launch_bounds__(kBlock) void k_router_hdrs(const uint8_t* __restric
     o[4] = h.w[4];
     const uint32_t slot = (lane64 >> 1) * 5;
     for (uint32_t k = lane; k < 5; k += 2) sw[slot + k] = fwd ? o[k] : 0u;
-    if (valid && lane == 0) status[i] = fwd ? 1 : 0;
+    if constexpr (kRoute) {
+      if (valid && lane == 0) {
+        uint32_t r_if = kNoRoute, r_hop = 0u;
+        const bool routed = fwd && route_find(rt, __builtin_bswap32(h.w[4]), r_if, r_hop);
+        status[i] = fwd ? (routed ? 3 : 1) : 0;
+        if (rt_iface) rt_iface[i] = r_if;
+        if (rt_hop) rt_hop[i] = r_hop;
+      }
+    } else {
+      if (valid && lane == 0) status[i] = fwd ? 1 : 0;
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -170,15 +201,29 @@ __global__ __launch_bounds__(kBlock) void k_router_hdrs(const uint8_t* __restric
 }  // namespace
 
 hipError_t launch_router_hdrs(const SegSpec& sp, uint32_t* hdr_out, uint8_t* status, hipStream_t st) {
-  hipLaunchKernelGGL(k_router_hdrs, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st, sp.bytes, sp.offsets, sp.stride,
-                     sp.seg_len, sp.n, hdr_out, status, static_cast<const uint32_t*>(sp.zero16));
+  hipLaunchKernelGGL(k_router_hdrs<false>, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st, sp.bytes, sp.offsets,
+                     sp.stride, sp.seg_len, sp.n, hdr_out, status, static_cast<const uint32_t*>(sp.zero16),
+                     RouteImg{}, nullptr, nullptr);
   return hipGetLastError();
 }
 
 hipError_t launch_router_ttl(const SegSpec& sp, uint8_t* status, hipStream_t st) {
-  hipLaunchKernelGGL(k_router_ttl, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st,
+  hipLaunchKernelGGL(k_router_ttl<false>, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st,
                      const_cast<uint8_t*>(sp.bytes), sp.offsets, sp.stride, sp.seg_len, sp.n, status,
-                     static_cast<const uint32_t*>(sp.zero16));
+                     static_cast<const uint32_t*>(sp.zero16), RouteImg{}, nullptr, nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_router_route(const SegSpec& sp, const RouteImg& t, uint32_t* hdr_out, uint8_t* status,
+                               uint32_t* iface, uint32_t* next_hop, hipStream_t st) {
+  const uint32_t* zpad = static_cast<const uint32_t*>(sp.zero16);
+  if (hdr_out)
+    hipLaunchKernelGGL(k_router_hdrs<true>, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st, sp.bytes, sp.offsets,
+                       sp.stride, sp.seg_len, sp.n, hdr_out, status, zpad, t, iface, next_hop);
+  else
+    hipLaunchKernelGGL(k_router_ttl<true>, dim3(ew_blocks(sp.n * 2)), dim3(kBlock), 0, st,
+                       const_cast<uint8_t*>(sp.bytes), sp.offsets, sp.stride, sp.seg_len, sp.n, status, zpad, t,
+                       iface, next_hop);
   return hipGetLastError();
 }
 

@@ -53,6 +53,53 @@ def _count(n, offsets, data, stride):
     return data.numel() // stride
 
 
+class RouteTable:
+    """ics_route_table_*: a route table with Router::match's semantics
+    (src/router/router.cpp:15-24, :77-87; include/icsum.h has the rules).
+    Needs no Engine and no GPU.  debug=True: a table of libicsum_debug.so,
+    for an Engine(debug=True) — a table belongs to the library that made it."""
+
+    def __init__(self, debug=False):
+        self.debug = bool(debug)
+        self.lib = _lib.load(_lib.DEBUG_LIB_PATH if debug else None)
+        h = ctypes.c_void_p()
+        check(self.lib.ics_route_table_create(ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def add(self, prefix, prefix_len, iface, next_hop=None):
+        """Router::add_route; next_hop None = a direct route (0 is a next hop
+        of 0.0.0.0, not "direct")."""
+        check(self.lib.ics_route_table_add(self.handle, prefix & 0xFFFFFFFF, prefix_len, iface,
+                                           next_hop is not None, (next_hop or 0) & 0xFFFFFFFF), self.lib)
+
+    def clear(self):
+        check(self.lib.ics_route_table_clear(self.handle), self.lib)
+
+    def match(self, addr):
+        """(iface, next_hop.value_or(addr)) or None."""
+        f, h = ctypes.c_uint32(), ctypes.c_uint32()
+        rc = self.lib.ics_route_table_match(self.handle, addr & 0xFFFFFFFF, ctypes.byref(f), ctypes.byref(h))
+        if rc < 0:
+            check(rc, self.lib)
+        return (f.value, h.value) if rc else None
+
+    def stats(self):
+        st = _lib.RouteStats()
+        check(self.lib.ics_route_table_stats(self.handle, ctypes.byref(st)), self.lib)
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def close(self):
+        if self.handle:
+            self.lib.ics_route_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One engine context bound to one GPU (ics_create / ics_destroy)."""
 
@@ -235,6 +282,51 @@ class Engine:
         self._check(self.lib.ics_router_ttl_headers(self.ctx, _ptr(dgrams), _ptr(offsets), stride, dgram_len, n,
                                                     _ptr(hdrs), _ptr(status), _stream(stream, self.device)))
         return hdrs, status
+
+    # ---- Router::match on the device ---------------------------------------
+    def _table(self, table):
+        if table.lib is not self.lib:
+            raise ValueError("the route table belongs to the other library build (RouteTable(debug=...))")
+        return table.handle
+
+    def route_lookup_batch(self, table, addrs, n=None, iface=None, next_hop=None, stream=None):
+        """match(addrs[i]) for a device tensor of host-order uint32 addresses
+        (int32 storage); returns (iface, next_hop) int32 tensors, 0xFFFFFFFF /
+        0 where no route matches."""
+        n = addrs.numel() if n is None else int(n)
+        iface = torch.empty(n, dtype=torch.int32, device=self.device) if iface is None else iface
+        next_hop = torch.empty(n, dtype=torch.int32, device=self.device) if next_hop is None else next_hop
+        self._check(self.lib.ics_route_lookup_batch(self.ctx, self._table(table), _ptr(addrs), n, _ptr(iface),
+                                                    _ptr(next_hop), _stream(stream, self.device)))
+        return iface, next_hop
+
+    def router_route_batch(self, table, dgrams, n=None, offsets=None, stride=0, dgram_len=0, status=None,
+                           iface=None, next_hop=None, stream=None):
+        """Router::route in place: router_ttl_batch's step, then match(dst) of
+        every datagram that forwards.  Returns (status, iface, next_hop);
+        status bit 0 = forwarded, bit 1 = routed."""
+        n = _count(n, offsets, dgrams, stride)
+        status = torch.empty(n, dtype=torch.uint8, device=self.device) if status is None else status
+        iface = torch.empty(n, dtype=torch.int32, device=self.device) if iface is None else iface
+        next_hop = torch.empty(n, dtype=torch.int32, device=self.device) if next_hop is None else next_hop
+        self._check(self.lib.ics_router_route_batch(self.ctx, self._table(table), _ptr(dgrams), _ptr(offsets), stride,
+                                                    dgram_len, n, _ptr(status), _ptr(iface), _ptr(next_hop),
+                                                    _stream(stream, self.device)))
+        return status, iface, next_hop
+
+    def router_route_headers(self, table, dgrams, n=None, offsets=None, stride=0, dgram_len=0, hdrs=None,
+                             status=None, iface=None, next_hop=None, stream=None):
+        """The same with the forwarded 20-byte headers into `hdrs` (as
+        router_ttl_headers); returns (hdrs, status, iface, next_hop)."""
+        n = _count(n, offsets, dgrams, stride)
+        hdrs = torch.empty(n * 20, dtype=torch.uint8, device=self.device) if hdrs is None else hdrs
+        status = torch.empty(n, dtype=torch.uint8, device=self.device) if status is None else status
+        iface = torch.empty(n, dtype=torch.int32, device=self.device) if iface is None else iface
+        next_hop = torch.empty(n, dtype=torch.int32, device=self.device) if next_hop is None else next_hop
+        self._check(self.lib.ics_router_route_headers(self.ctx, self._table(table), _ptr(dgrams), _ptr(offsets),
+                                                      stride, dgram_len, n, _ptr(hdrs), _ptr(status), _ptr(iface),
+                                                      _ptr(next_hop), _stream(stream, self.device)))
+        return hdrs, status, iface, next_hop
 
     # ---- host-memory (PCIe-inclusive) variants -----------------------------
     def checksum_batch_host(self, data, n, offsets=None, stride=0, seg_len=0, init=None, out=None):
