@@ -63,18 +63,28 @@ class RouteStats(ctypes.Structure):
                 ("image_words", ctypes.c_uint64), ("l2_chunks", ctypes.c_uint64), ("l3_chunks", ctypes.c_uint64)]
 
 
+class NeighStats(ctypes.Structure):
+    """struct ics_neigh_stats_t (include/icsum.h)."""
+    _fields_ = [("ifaces", ctypes.c_uint64), ("mappings", ctypes.c_uint64), ("pending_requests", ctypes.c_uint64),
+                ("image_ifaces", ctypes.c_uint64), ("image_slots", ctypes.c_uint64), ("generation", ctypes.c_uint64)]
+
+
 # ICS_K_* kernel ids of ics_dispatch_info_t.last_kernel
 KERNELS = {1: "checksum", 2: "small", 3: "tiny", 4: "dense", 5: "twoclass", 6: "binned", 7: "ipv4",
            8: "ipv4_twoclass", 9: "wrap", 10: "wrap_2pass", 11: "router", 12: "batchv", 13: "tile",
            14: "router_hdrs", 15: "tick", 16: "tick_server", 17: "route_lookup", 18: "router_route",
-           19: "router_route_hdrs"}
+           19: "router_route_hdrs", 20: "frame_recv", 21: "router_frames"}
 ICS_RT_FORWARD, ICS_RT_ROUTED = 0x01, 0x02
 ICS_NO_ROUTE = 0xFFFFFFFF
+ICS_FR_RESOLVED, ICS_FR_DGRAM, ICS_FR_FOR_US, ICS_FR_IPV4, ICS_FR_ARP, ICS_FR_ARP_OK = 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
+ICS_ARP_REPLY, ICS_ARP_RELEASE, ICS_ARP_REQUEST = 0x01, 0x02, 0x04
+ICS_ALL_IFACES = 0xFFFFFFFF
 
 _p = ctypes.c_void_p
 _u64 = ctypes.c_uint64
 _int = ctypes.c_int
 _u32 = ctypes.c_uint32
+_pu32 = ctypes.POINTER(ctypes.c_uint32)
 
 # name -> (restype, argtypes); every symbol include/icsum.h and
 # include/icsum_workload.h declare
@@ -104,6 +114,18 @@ SIGNATURES = {
     "ics_route_lookup_batch": (_int, [_p, _p, _p, _u64, _p, _p, _p]),
     "ics_router_route_batch": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "ics_router_route_headers": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
+    "ics_neigh_table_create": (_int, [ctypes.POINTER(_p)]),
+    "ics_neigh_table_destroy": (_int, [_p]),
+    "ics_neigh_table_set_iface": (_int, [_p, _u32, _p, _u32]),
+    "ics_neigh_table_learn": (_int, [_p, _u32, _u32, _p]),
+    "ics_neigh_table_lookup": (_int, [_p, _u32, _u32, _p]),
+    "ics_neigh_table_tick": (_int, [_p, _u32, _u64]),
+    "ics_neigh_table_recv_frame": (_int, [_p, _u32, _p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint8), _pu32,
+                                          _pu32, _p]),
+    "ics_neigh_table_resolve": (_int, [_p, _u32, _u32, _p, _pu32, _p]),
+    "ics_neigh_table_stats": (_int, [_p, ctypes.POINTER(NeighStats)]),
+    "ics_frame_recv_batch": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _u32, _p, _p, _p]),
+    "ics_router_frames": (_int, [_p, _p, _p, _p, _p, _u64, _u64, _u64, _u32, _p, _p, _p, _p, _p, _p]),
     "ics_tcp_wrap_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p]),
     "ics_tcp_wrap_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p]),
     "ics_tcp_wrap_headers": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p, _p]),

@@ -52,10 +52,14 @@ int bounds_verdict(hipStream_t st, int rc) {
   ICS_HIP(icsum::bounds_take(st, &flags, &what));
   if (flags)
     return fail(ICS_ERR_INVALID,
-                "bounds check: %s%s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
+                "bounds check: %s%s%s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
                 (flags & 2u) ? "offsets not monotone " : "", (flags & 4u) ? "header load past a datagram " : "",
                 (flags & 8u) ? "route image index outside the image " : "",
-                (flags & 2u) && !(flags & 13u) ? "segment" : (flags & 8u) && !(flags & 7u) ? "image word" : "address",
+                (flags & 16u) ? "neighbour image slot outside the table " : "",
+                (flags & 2u) && !(flags & 29u)   ? "segment"
+                : (flags & 8u) && !(flags & 23u)  ? "image word"
+                : (flags & 16u) && !(flags & 15u) ? "image slot"
+                                                  : "address",
                 (unsigned long long)what);
   return ICS_OK;
 }
@@ -364,6 +368,39 @@ int ics_router_route_headers(ics_ctx* ctx, ics_route_table* tbl, const void* d_d
   hipStream_t st = static_cast<hipStream_t>(stream);
   return bounds_verdict(st, route_device(ctx, tbl, &sp, nullptr, n, static_cast<uint32_t*>(d_hdrs), d_status, d_iface,
                                          d_next_hop, st));
+}
+
+int ics_frame_recv_batch(ics_ctx* ctx, ics_neigh_table* neigh, const void* d_frames, const uint64_t* d_offsets,
+                         uint64_t stride, uint64_t frame_len, uint64_t n, uint32_t in_iface,
+                         const uint32_t* d_in_iface, uint8_t* d_status, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (!neigh) return fail(ICS_ERR_INVALID, "null neighbour table");
+  if (n == 0) return ICS_OK;
+  if (!d_frames || !d_status) return fail(ICS_ERR_INVALID, "null device buffer");
+  if (reinterpret_cast<uintptr_t>(d_in_iface) & 3u) return fail(ICS_ERR_INVALID, "ingress interface array not 4-byte aligned");
+  const icsum::SegSpec sp{static_cast<const uint8_t*>(d_frames), d_offsets, stride, frame_len, n, ctx->d_zero};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, frames_device(ctx, nullptr, neigh, sp, in_iface, d_in_iface, nullptr, d_status, nullptr,
+                                          nullptr, st));
+}
+
+int ics_router_frames(ics_ctx* ctx, ics_route_table* routes, ics_neigh_table* neigh, const void* d_frames,
+                      const uint64_t* d_offsets, uint64_t stride, uint64_t frame_len, uint64_t n, uint32_t in_iface,
+                      const uint32_t* d_in_iface, void* d_hdrs, uint8_t* d_status, uint32_t* d_iface,
+                      uint32_t* d_next_hop, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (!routes) return fail(ICS_ERR_INVALID, "null route table");
+  if (!neigh) return fail(ICS_ERR_INVALID, "null neighbour table");
+  if (n == 0) return ICS_OK;
+  if (!d_frames || !d_hdrs || !d_status) return fail(ICS_ERR_INVALID, "null device buffer");
+  if (reinterpret_cast<uintptr_t>(d_hdrs) & 3u) return fail(ICS_ERR_INVALID, "record array not 4-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(d_iface) | reinterpret_cast<uintptr_t>(d_next_hop) |
+       reinterpret_cast<uintptr_t>(d_in_iface)) & 3u)
+    return fail(ICS_ERR_INVALID, "interface / next-hop arrays not 4-byte aligned");
+  const icsum::SegSpec sp{static_cast<const uint8_t*>(d_frames), d_offsets, stride, frame_len, n, ctx->d_zero};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, frames_device(ctx, routes, neigh, sp, in_iface, d_in_iface, static_cast<uint32_t*>(d_hdrs),
+                                          d_status, d_iface, d_next_hop, st));
 }
 
 int ics_checksum_batch_host(ics_ctx* ctx, const void* h_bytes, const uint64_t* h_offsets,

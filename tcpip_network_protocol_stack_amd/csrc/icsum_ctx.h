@@ -255,6 +255,10 @@ struct ics_ctx {
     bool launched = false;
   };
   RouteSlot route_slot[kRouteSlots];
+  // neighbour images (ics_frame_recv_batch, ics_router_frames), kept the same
+  // way under the same lock: nwords holds the identity entries, nrecs the
+  // hash slots of the image (csrc/icsum_neigh.h)
+  RouteSlot neigh_slot[kRouteSlots];
   uint64_t route_clock = 0;
   std::vector<void*> route_retired;
   std::mutex route_mu;
@@ -341,7 +345,13 @@ int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint
 // as router_device).  Brings the table's image up to date on `st` first.
 int route_device(ics_ctx* ctx, ics_route_table* tbl, const icsum::SegSpec* sp, const uint32_t* d_addrs, uint64_t n,
                  uint32_t* d_hdrs, uint8_t* d_status, uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st);
-// Release the route images (ics_destroy).
+// Ethernet frames: routes null = recv_frame's classification alone (d_hdrs,
+// d_iface, d_next_hop unused), else the whole hop with 36-byte records to
+// d_hdrs.  Brings both tables' images up to date on `st` first.
+int frames_device(ics_ctx* ctx, ics_route_table* routes, ics_neigh_table* neigh, const icsum::SegSpec& sp,
+                  uint32_t in_iface, const uint32_t* d_in_iface, uint32_t* d_hdrs, uint8_t* d_status,
+                  uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st);
+// Release the route and neighbour images (ics_destroy).
 void free_routes(ics_ctx* ctx);
 // Multi-batch calls: batches grouped by kernel shape, one launch per group.
 int checksum_batchv_device(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, hipStream_t st);

@@ -26,6 +26,7 @@
 //   icsum_tick.h        k_tick, k_tick_server
 //   icsum_route.h       the route image walk (Router::match), k_route_lookup
 //   icsum_router.h      k_router_ttl, k_router_hdrs (<true>: the route lookup fused)
+//   icsum_frame.h       k_frame (<false>: recv_frame's classification, <true>: the hop over Ethernet frames)
 //   icsum_span.h        k_span (tile launches)
 //   icsum_generators.h  the workload generators
 // (icsum_device.h: arithmetic primitives; icsum_launch.h: the launchers' interface)
@@ -38,6 +39,7 @@
 #include "icsum_tick.h"
 #include "icsum_route.h"
 #include "icsum_router.h"
+#include "icsum_frame.h"
 #include "icsum_span.h"
 #include "icsum_generators.h"
 

@@ -197,6 +197,21 @@ hipError_t launch_route_lookup(const uint32_t* addrs, uint64_t n, const RouteImg
 hipError_t launch_router_route(const SegSpec& sp, const RouteImg& t, uint32_t* hdr_out, uint8_t* status,
                                uint32_t* iface, uint32_t* next_hop, hipStream_t st);
 
+// Ethernet frames (kernels/icsum_frame.h).  A neighbour table's compiled image
+// in device memory (csrc/icsum_neigh.h has the layout): 4 * nif identity words,
+// then 4 * nslots slot words, 16-byte aligned.
+struct NeighImg {
+  const uint32_t* words;
+  uint32_t nif;
+  uint32_t nslots;  // a power of two
+};
+// recv_frame's classification (hdr_out null, no route image read: k_frame<false>)
+// or the whole hop (k_frame<true>): 36-byte records to hdr_out, iface /
+// next_hop nullable.  in_ifaces null: every frame arrived on in_iface.
+hipError_t launch_frames(const SegSpec& sp, const RouteImg& rt, const NeighImg& nb, uint32_t in_iface,
+                         const uint32_t* in_ifaces, uint32_t* hdr_out, uint8_t* status, uint32_t* iface,
+                         uint32_t* next_hop, hipStream_t st);
+
 // Tile launches of offsets batches (k_span): one wave per S (1..63)
 // consecutive segments, the span's bytes streamed whole in 4 KiB windows
 // whatever the lengths.  Checksum (out_kind as launch_checksum), the fused IPv4/TCP kernel

@@ -100,6 +100,79 @@ class RouteTable:
             pass
 
 
+class NeighTable:
+    """ics_neigh_table_*: the control half of the router's NetworkInterfaces
+    (src/network_interface/network_interface.cpp; include/icsum.h has the
+    rules) — per-interface addresses, ARP cache and pending requests.  Needs
+    no Engine and no GPU.  Addresses are 6-byte `bytes`, ips host-order ints.
+    The queue of datagrams waiting for a reply is the caller's.  debug=True: a
+    table of libicsum_debug.so, for an Engine(debug=True)."""
+
+    def __init__(self, debug=False):
+        self.debug = bool(debug)
+        self.lib = _lib.load(_lib.DEBUG_LIB_PATH if debug else None)
+        h = ctypes.c_void_p()
+        check(self.lib.ics_neigh_table_create(ctypes.byref(h)), self.lib)
+        self.handle = h
+
+    def set_iface(self, iface, mac, ip):
+        """NetworkInterface's constructor: interface `iface` has these addresses."""
+        check(self.lib.ics_neigh_table_set_iface(self.handle, iface, bytes(mac), ip & 0xFFFFFFFF), self.lib)
+
+    def learn(self, iface, ip, mac):
+        check(self.lib.ics_neigh_table_learn(self.handle, iface, ip & 0xFFFFFFFF, bytes(mac)), self.lib)
+
+    def lookup(self, iface, ip):
+        """the neighbour's address (bytes) or None; walks the compiled image"""
+        mac = ctypes.create_string_buffer(6)
+        rc = self.lib.ics_neigh_table_lookup(self.handle, iface, ip & 0xFFFFFFFF, mac)
+        if rc < 0:
+            check(rc, self.lib)
+        return mac.raw if rc else None
+
+    def tick(self, ms, iface=_lib.ICS_ALL_IFACES):
+        check(self.lib.ics_neigh_table_tick(self.handle, iface, int(ms)), self.lib)
+
+    def recv_frame(self, iface, frame):
+        """recv_frame for one frame: (status, events, sender_ip, reply) — reply
+        is the 42-byte ARP reply to transmit when events has ICS_ARP_REPLY,
+        else None."""
+        frame = bytes(frame)
+        st, ev, sip = ctypes.c_uint8(), ctypes.c_uint32(), ctypes.c_uint32()
+        reply = ctypes.create_string_buffer(42)
+        check(self.lib.ics_neigh_table_recv_frame(self.handle, iface, frame, len(frame), ctypes.byref(st),
+                                                  ctypes.byref(ev), ctypes.byref(sip), reply), self.lib)
+        return st.value, ev.value, sip.value, reply.raw if ev.value & _lib.ICS_ARP_REPLY else None
+
+    def resolve(self, iface, next_hop):
+        """send_datagram's control half: (hdr14, None) on a hit, else (None,
+        request) with the 42-byte ARP request to transmit, or (None, None)
+        while one is pending (or the interface has no addresses)."""
+        hdr, req, ev = ctypes.create_string_buffer(14), ctypes.create_string_buffer(42), ctypes.c_uint32()
+        rc = self.lib.ics_neigh_table_resolve(self.handle, iface, next_hop & 0xFFFFFFFF, hdr, ctypes.byref(ev), req)
+        if rc < 0:
+            check(rc, self.lib)
+        if rc:
+            return hdr.raw, None
+        return None, req.raw if ev.value & _lib.ICS_ARP_REQUEST else None
+
+    def stats(self):
+        st = _lib.NeighStats()
+        check(self.lib.ics_neigh_table_stats(self.handle, ctypes.byref(st)), self.lib)
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def close(self):
+        if self.handle:
+            self.lib.ics_neigh_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One engine context bound to one GPU (ics_create / ics_destroy)."""
 
@@ -326,6 +399,42 @@ class Engine:
         self._check(self.lib.ics_router_route_headers(self.ctx, self._table(table), _ptr(dgrams), _ptr(offsets),
                                                       stride, dgram_len, n, _ptr(hdrs), _ptr(status), _ptr(iface),
                                                       _ptr(next_hop), _stream(stream, self.device)))
+        return hdrs, status, iface, next_hop
+
+    # ---- Ethernet frames through the hop -----------------------------------
+    def _neigh(self, table):
+        if table.lib is not self.lib:
+            raise ValueError("the neighbour table belongs to the other library build (NeighTable(debug=...))")
+        return table.handle
+
+    def frame_recv(self, neigh, frames, n=None, offsets=None, stride=0, frame_len=0, in_iface=0, in_ifaces=None,
+                   status=None, stream=None):
+        """recv_frame's classification of n Ethernet frames that arrived on
+        in_iface (or in_ifaces[i], an int32 device tensor): the ICS_FR_* bits
+        per frame.  The frames are only read."""
+        n = _count(n, offsets, frames, stride)
+        status = torch.empty(n, dtype=torch.uint8, device=self.device) if status is None else status
+        self._check(self.lib.ics_frame_recv_batch(self.ctx, self._neigh(neigh), _ptr(frames), _ptr(offsets), stride,
+                                                  frame_len, n, in_iface, _ptr(in_ifaces), _ptr(status),
+                                                  _stream(stream, self.device)))
+        return status
+
+    def router_frames(self, routes, neigh, frames, n=None, offsets=None, stride=0, frame_len=0, in_iface=0,
+                      in_ifaces=None, hdrs=None, status=None, iface=None, next_hop=None, stream=None):
+        """The whole hop: classification, Router::route on the datagram at
+        frame + 14, and the neighbour lookup on the egress interface, against
+        the neighbour table as of the call.  Returns (hdrs, status, iface,
+        next_hop); hdrs holds one 36-byte record per frame (2 zero bytes, the
+        Ethernet header, the 20 forwarded header bytes)."""
+        n = _count(n, offsets, frames, stride)
+        hdrs = torch.empty(n * 36, dtype=torch.uint8, device=self.device) if hdrs is None else hdrs
+        status = torch.empty(n, dtype=torch.uint8, device=self.device) if status is None else status
+        iface = torch.empty(n, dtype=torch.int32, device=self.device) if iface is None else iface
+        next_hop = torch.empty(n, dtype=torch.int32, device=self.device) if next_hop is None else next_hop
+        self._check(self.lib.ics_router_frames(self.ctx, self._table(routes), self._neigh(neigh), _ptr(frames),
+                                               _ptr(offsets), stride, frame_len, n, in_iface, _ptr(in_ifaces),
+                                               _ptr(hdrs), _ptr(status), _ptr(iface), _ptr(next_hop),
+                                               _stream(stream, self.device)))
         return hdrs, status, iface, next_hop
 
     # ---- host-memory (PCIe-inclusive) variants -----------------------------

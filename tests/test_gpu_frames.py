@@ -1,0 +1,485 @@
+"""GPU: Ethernet frames through the router hop — ics_frame_recv_batch
+(k_frame<false>, recv_frame's classification) and ics_router_frames
+(k_frame<true>: classification, Router::route, the neighbour lookup on the
+egress interface and make_frame's header).
+
+References: the real reference's transmitted frames (tests/golden/frame_cases.json)
+for the golden bursts; the Python restatement (frame_ref.py, pinned to the
+reference in test_neigh_table.py) for every status bit and record byte; and the
+merged ics_router_route_headers on the same datagrams (frames minus 14 bytes)
+for the forward decision, the 20 header bytes and the route answer.  Every
+test runs in the release build and in libicsum_debug.so, whose kernel checks
+every header load against the frame and every slot index against the image.
+Bar: exact."""
+import copy
+import ctypes
+
+import numpy as np
+import pytest
+
+from conftest import engine_with
+from frame_ref import (FR_ARP, FR_ARP_OK, FR_DGRAM, FR_FOR_US, FR_IPV4, FR_RESOLVED, RT_FORWARD, RT_ROUTED, RefNeigh,
+                       classify, forward_header, header_sum, load_golden, neigh_hash, replay, slots_for)
+from route_ref import NO_ROUTE, RefRouter, fill
+from test_gpu_parity import _t, _u32
+
+pytestmark = pytest.mark.gpu
+
+MACS = {k: bytes([0x02, 0x10, 0x20, 0x30, 0x40, k]) for k in (0, 1, 2, 3)}
+IPS = {0: 0x0A000001, 1: 0x0A000101, 2: 0xC0A80701, 3: 0xAC100001}
+ROUTES = [
+    (0x0A000000, 24, 0, False, 0),
+    (0x0A000100, 24, 1, False, 0),
+    (0xC0A80700, 24, 2, False, 0),
+    (0xAC100000, 12, 3, True, 0xAC1000FE),
+    (0x08080000, 16, 1, True, 0x0A0001FE),
+    (0x09000000, 8, 9, False, 0),           # an interface that has no addresses: never resolved
+    (0x0B000000, 8, 2, True, 0x0A000114),   # the next hop is known on interface 1 only
+]
+# (iface, ip): neighbours the table knows
+NEIGH = [(0, 0x0A000007), (1, 0x0A000114), (1, 0x0A0001FE), (2, 0xC0A807FE), (3, 0xAC1000FE), (1, 0x0A000115),
+         (9, 0x09000001)]
+# destinations: resolved direct / via gateway, unresolved, unrouted, unconfigured egress, wrong interface's cache
+DSTS = [0x0A000007, 0x0A000114, 0x0A000115, 0xC0A807FE, 0xAC100102, 0x08080808, 0x0A000116, 0xC0A80709, 0x0A000008,
+        0x0C000001, 0x7F000001, 0x09000001, 0x0B000001]
+
+
+def _nmac(iface, ip):
+    return bytes([0x06, iface]) + ip.to_bytes(4, "big")
+
+
+def _fill_neigh(t):
+    for k in MACS:
+        t.set_iface(k, MACS[k], IPS[k])
+    for f, ip in NEIGH:
+        t.learn(f, ip, _nmac(f, ip))
+    return t
+
+
+@pytest.fixture(scope="module", params=[False, True], ids=["release", "debug"])
+def hop(request):
+    """(engine, RouteTable, NeighTable, RefRouter, RefNeigh) of one library build"""
+    from tcpip_network_protocol_stack_amd.engine import NeighTable, RouteTable
+
+    gen = engine_with(None, debug=request.param)
+    eng = next(gen)
+    routes = fill(RouteTable(debug=request.param), ROUTES)
+    neigh = _fill_neigh(NeighTable(debug=request.param))
+    yield eng, routes, neigh, RefRouter(ROUTES), _fill_neigh(RefNeigh())
+    next(gen, None)
+    routes.close()
+    neigh.close()
+
+
+# ------------------------------------------------------------ expectations --
+def expect(frames, ins, router, neigh):
+    """(status, iface, next_hop, records) the whole hop must give"""
+    n = len(frames)
+    st, fi, fh = np.zeros(n, np.uint8), np.full(n, NO_ROUTE, np.uint32), np.zeros(n, np.uint32)
+    rec = np.zeros((n, 36), np.uint8)
+    for i, (f, k) in enumerate(zip(frames, ins)):
+        me = neigh.ident.get(int(k))
+        s = classify(f, me[0] if me else None)
+        if s & FR_DGRAM:
+            p = f[14:]
+            hdr = forward_header(p)
+            if hdr is not None:
+                s |= RT_FORWARD
+                rec[i, 16:36] = np.frombuffer(hdr, np.uint8)
+                hit = router.answer(int.from_bytes(p[16:20], "big"))
+                if hit is not None:
+                    s |= RT_ROUTED
+                    fi[i], fh[i] = hit
+                    out = neigh.ident.get(hit[0])
+                    mac = neigh.lookup(hit[0], hit[1])
+                    if out is not None and mac is not None:
+                        s |= FR_RESOLVED
+                        rec[i, 2:16] = np.frombuffer(mac + out[0] + b"\x08\x00", np.uint8)
+        st[i] = s
+    return st, fi, fh, rec
+
+
+def check_invariants(st):
+    st = st.astype(np.uint32)
+    for a, b in ((FR_RESOLVED, RT_ROUTED), (RT_ROUTED, RT_FORWARD), (RT_FORWARD, FR_DGRAM), (FR_DGRAM, FR_IPV4),
+                 (FR_IPV4, FR_FOR_US), (FR_ARP_OK, FR_ARP), (FR_ARP, FR_FOR_US)):
+        assert not ((st & a != 0) & (st & b == 0)).any(), (a, b)
+    assert not ((st & FR_IPV4 != 0) & (st & FR_ARP != 0)).any()
+
+
+def _sentinel(n, dtype, value):
+    import torch
+
+    return torch.full((n,), value, dtype=dtype, device="cuda:0")
+
+
+def run_hop(eng, routes, neigh, d, n, ins=None, in_iface=0, tail=64, **kw):
+    """both calls on the device batch `d`; returns (recv status, status, iface, next_hop, records) and
+    checks the dispatch ids, the sentinel behind the records and the invariants"""
+    import torch
+
+    st0 = _sentinel(n, torch.uint8, 0x5A)
+    dins = None if ins is None else _t(np.asarray(ins, np.uint32))
+    eng.frame_recv(neigh, d, n=n, in_iface=in_iface, in_ifaces=dins, status=st0, **kw)
+    assert eng.dispatch_info()["kernel"] == "frame_recv"
+    hd, st = _sentinel(n * 36 + tail, torch.uint8, 0xA5), _sentinel(n, torch.uint8, 0x5A)
+    f, h = _sentinel(n, torch.int32, 0x25A5A5A5), _sentinel(n, torch.int32, 0x25A5A5A5)
+    eng.router_frames(routes, neigh, d, n=n, in_iface=in_iface, in_ifaces=dins, hdrs=hd, status=st, iface=f,
+                      next_hop=h, **kw)
+    assert eng.dispatch_info()["kernel"] == "router_frames"
+    hd = hd.cpu().numpy()
+    assert (hd[n * 36:] == 0xA5).all()  # nothing written behind the last record
+    rec = hd[:n * 36].reshape(n, 36)
+    assert (rec[:, :2] == 0).all()
+    st0, st = st0.cpu().numpy(), st.cpu().numpy()
+    check_invariants(st)
+    check_invariants(st0)
+    assert (st0 == (st & 0xF8)).all()
+    assert (rec[(st & RT_FORWARD) == 0] == 0).all() and (rec[(st & FR_RESOLVED) == 0][:, :16] == 0).all()
+    return st0, st, _u32(f), _u32(h), rec
+
+
+def check_hop(eng, routes, neigh, router, rneigh, frames, ins, d, n, tag, uniform=None, **kw):
+    want_st, want_f, want_h, want_rec = expect(frames, ins, router, rneigh)
+    st0, st, f, h, rec = run_hop(eng, routes, neigh, d, n, ins=None if uniform is not None else ins,
+                                 in_iface=uniform or 0, **kw)
+    assert (st == want_st).all(), (tag, np.flatnonzero(st != want_st)[:8], st[st != want_st][:8],
+                                   want_st[st != want_st][:8])
+    assert (f == want_f).all() and (h == want_h).all(), tag
+    assert (rec == want_rec).all(), (tag, np.flatnonzero((rec != want_rec).any(axis=1))[:8])
+    return want_st
+
+
+# ---------------------------------------------------------------- inputs ---
+def make_frame(rng, length, in_iface):
+    """one frame of exactly `length` bytes arriving on in_iface, its kind drawn at random"""
+    if length < 14:
+        return bytes(int(b) for b in rng.integers(0, 256, length))
+    r = rng.random()
+    me = MACS.get(in_iface, MACS[0])
+    dst = (me if r < 0.72 else b"\xff" * 6 if r < 0.82 else bytes([2, 0x10, 0x20, 0x30, 0x40, 0x99]) if r < 0.88
+           else bytes([1, 0, 0x5E, 0, 0, 1]) if r < 0.92 else MACS[(in_iface + 1) % 4] if r < 0.96
+           else me[:5] + bytes([me[5] ^ 0x80]))
+    r = rng.random()
+    etype = b"\x08\x00" if r < 0.7 else b"\x08\x06" if r < 0.88 else [b"\x86\xdd", b"\x00\x00", b"\x00\x08"][int(
+        rng.integers(0, 3))]
+    plen = length - 14
+    p = bytearray(int(b) for b in rng.integers(0, 256, max(plen, 28)))
+    if etype == b"\x08\x06":
+        p[0:8] = b"\x00\x01\x08\x00\x06\x04\x00" + bytes([int(rng.integers(1, 3))])
+        if rng.random() < 0.3:
+            k = int(rng.integers(0, 8))
+            p[k] ^= 1 << int(rng.integers(0, 8))
+    else:
+        r = rng.random()
+        p[0] = 0x45 if r < 0.6 else 0x46 if r < 0.7 else 0x4F if r < 0.75 else 0x44 if r < 0.8 else 0x65 if r < 0.85 else 0x45
+        p[6] = (p[6] | 0x80) if rng.random() < 0.2 else (p[6] & 0x7F)
+        p[8] = int(rng.choice([0, 1, 2, 3, 64, 255]))
+        p[16:20] = int(DSTS[int(rng.integers(0, len(DSTS)))]).to_bytes(4, "big")
+        c = header_sum(p)
+        p[10], p[11] = c >> 8, c & 0xFF
+        if rng.random() < 0.1:
+            p[11] ^= 1
+    return dst + bytes([2, 0, 0, 0, 0, 0x55]) + etype + bytes(p[:plen])
+
+
+def make_burst(seed, lengths, n_ifaces=4):
+    rng = np.random.default_rng(seed)
+    ins = rng.integers(0, n_ifaces + 1, len(lengths))  # interface 4 has no addresses
+    ins[ins == 4] = np.where(rng.random((ins == 4).sum()) < 0.5, 7, 0)
+    return [make_frame(rng, int(L), int(k)) for L, k in zip(lengths, ins)], ins.astype(np.uint32)
+
+
+def _pack(segs):
+    """back-to-back segments from offset 0, nothing behind the last: (bytes, n + 1 offsets)"""
+    off = np.zeros(len(segs) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in segs])
+    return np.frombuffer(b"".join(segs) or b"\0", np.uint8).copy(), off
+
+
+MIX = [0, 13, 14, 33, 34, 41, 42, 60, 1514]
+
+
+def mixed_lengths(seed, n):
+    rng = np.random.default_rng(seed)
+    return rng.choice(MIX, n, p=[.03, .03, .04, .05, .2, .05, .2, .3, .1])
+
+
+# ------------------------------------------------------------------ tests --
+def test_golden_bursts(hop):
+    """every burst of the golden scenarios: status bits equal the restatement and every RESOLVED frame's
+    record[2:36] + payload piece is the frame the reference transmitted on d_iface[i], in batch order"""
+    from tcpip_network_protocol_stack_amd.engine import NeighTable, RouteTable
+
+    eng, _, table0, _, _ = hop
+    bursts = 0
+    for sc in load_golden():
+        if not any(e["op"] == "route" for e in sc["events"]):
+            continue
+        snaps = []
+        for _ in replay(sc, RefNeigh(), on_route=lambda h, b: snaps.append(copy.deepcopy(h.table))):
+            pass
+        router = RefRouter([tuple(r) for r in sc["routes"]])
+        routes = fill(RouteTable(debug=table0.debug), [tuple(r) for r in sc["routes"]])
+        neigh = NeighTable(debug=table0.debug)
+        sent = []
+
+        def on_route(h, burst):
+            order = sorted(range(len(burst)), key=lambda k: burst[k]["iface"])  # route() drains interface by interface
+            frames = [bytes.fromhex(burst[k]["frame"]) for k in order]
+            ins = np.array([burst[k]["iface"] for k in order], np.uint32)
+            buf, off = _pack(frames)
+            st = check_hop(eng, routes, h.table, router, snaps[len(sent)], frames, ins, _t(buf), len(frames),
+                           sc["name"], offsets=_t(off))
+            _, _, f, _, rec = run_hop(eng, routes, h.table, _t(buf), len(frames), ins=ins, offsets=_t(off))
+            out = [(int(f[i]), rec[i, 2:36].tobytes() + frames[i][14 + 4 * (frames[i][14] & 15):])
+                   for i in range(len(frames)) if st[i] & FR_RESOLVED]
+            sent.append(out)
+
+        k = 0
+        for ev, tx, _ in replay(sc, neigh, on_route=on_route):
+            assert tx == [(i, bytes.fromhex(f)) for i, f in ev["tx"]]
+            if ev["op"] == "route":
+                want = [(i, bytes.fromhex(f)) for i, f in ev["tx"] if f[24:28] == "0800"]
+                for ifc in range(len(sc["ifaces"])):
+                    assert [w for w in sent[k] if w[0] == ifc] == [w for w in want if w[0] == ifc], (sc["name"], k, ifc)
+                k += 1
+                bursts += 1
+        routes.close()
+        neigh.close()
+    assert bursts >= 4
+
+
+def test_random_burst_against_the_merged_router_call(hop):
+    """3000 frames of mixed lengths and every class; where FOR_US and IPV4 hold, status & 3, record[16:36],
+    d_iface and d_next_hop equal ics_router_route_headers on the datagrams (frames minus 14 bytes); zero or
+    no-route elsewhere"""
+    eng, routes, neigh, router, rneigh = hop
+    frames, ins = make_burst(0xF4A3E, mixed_lengths(1, 3000))
+    buf, off = _pack(frames)
+    n = len(frames)
+    want = check_hop(eng, routes, neigh, router, rneigh, frames, ins, _t(buf), n, "random", offsets=_t(off))
+    for bit in (FR_RESOLVED, RT_ROUTED, RT_FORWARD, FR_DGRAM, FR_IPV4, FR_FOR_US, FR_ARP, FR_ARP_OK):
+        assert (want & bit != 0).any(), bit
+    # every class: each implication of the chain is strict somewhere, and nothing-at-all occurs
+    for a, b in ((RT_ROUTED, FR_RESOLVED), (RT_FORWARD, RT_ROUTED), (FR_DGRAM, RT_FORWARD), (FR_IPV4, FR_DGRAM),
+                 (FR_FOR_US, FR_IPV4 | FR_ARP), (FR_ARP, FR_ARP_OK)):
+        assert ((want & a != 0) & (want & b == 0)).any(), (a, b)
+    assert (want == 0).any()
+    _, st, f, h, rec = run_hop(eng, routes, neigh, _t(buf), n, ins=ins, offsets=_t(off))
+    dg = [fr[14:] for fr in frames]
+    dbuf, doff = _pack(dg)
+    hd0, st0, f0, h0 = eng.router_route_headers(routes, _t(dbuf), n=n, offsets=_t(doff))
+    hd0, st0, f0, h0 = hd0.cpu().numpy().reshape(n, 20), st0.cpu().numpy(), _u32(f0), _u32(h0)
+    ours = (st & (FR_FOR_US | FR_IPV4)) == (FR_FOR_US | FR_IPV4)
+    assert ours.sum() > 500 and (~ours).sum() > 500
+    assert ((st & 3)[ours] == st0[ours]).all() and (rec[ours][:, 16:36] == hd0[ours]).all()
+    assert (f[ours] == f0[ours]).all() and (h[ours] == h0[ours]).all()
+    assert ((st & 7)[~ours] == 0).all() and (rec[~ours] == 0).all()
+    assert (f[~ours] == NO_ROUTE).all() and (h[~ours] == 0).all()
+    assert (st0[~ours] != 0).any()  # frames the bare datagram call would have forwarded, filtered here
+
+
+@pytest.mark.parametrize("n", [1, 31, 32, 33, 63, 64, 65, 2051])
+def test_counts_with_mixed_lengths(hop, n):
+    """a wave's partial last group of records, an idle lane group; per-frame ingress, then uniform ingress"""
+    eng, routes, neigh, router, rneigh = hop
+    frames, ins = make_burst(0xC0 + n, mixed_lengths(n, n) if n > 1 else [42])
+    if n == 1:
+        frames, ins = [MACS[0] + frames[0][6:]], np.array([0], np.uint32)
+    buf, off = _pack(frames)
+    check_hop(eng, routes, neigh, router, rneigh, frames, ins, _t(buf), n, n, offsets=_t(off))
+    for k in (1, 7):  # uniform ingress: a configured interface, one without addresses
+        uni = np.full(n, k, np.uint32)
+        st = check_hop(eng, routes, neigh, router, rneigh, frames, uni, _t(buf), n, (n, k), uniform=k, offsets=_t(off))
+        assert k != 7 or (st == 0).all()
+
+
+@pytest.mark.parametrize("stride", [14, 34, 42, 64, 1514, 1516])
+def test_fixed_strides(hop, stride):
+    eng, routes, neigh, router, rneigh = hop
+    n = 300 if stride > 1000 else 2051
+    frames, ins = make_burst(0x57 + stride, [stride] * n)
+    buf = np.frombuffer(b"".join(frames), np.uint8)
+    st = check_hop(eng, routes, neigh, router, rneigh, frames, ins, _t(buf), n, stride, stride=stride,
+                   frame_len=stride)
+    if stride >= 34:
+        assert (st & FR_RESOLVED != 0).any() and (st & RT_FORWARD != 0).any()
+    if stride >= 42:
+        assert (st & FR_ARP_OK != 0).any()
+    else:
+        assert (st & FR_ARP_OK == 0).all() and (st & FR_ARP != 0).any()
+    if stride == 14:
+        assert (st & FR_DGRAM == 0).all() and (st & FR_IPV4 != 0).any()
+
+
+@pytest.mark.parametrize("base", [0, 1, 2, 3])
+def test_any_base_and_the_buffers_last_byte(hop, base):
+    """the batch `base` bytes into an allocation that ends with the last frame's last byte; the last
+    frames have every length of the mix in turn"""
+    import torch
+
+    eng, routes, neigh, router, rneigh = hop
+    for last in MIX[2:]:
+        lengths = list(mixed_lengths(base * 16 + last, 200)) + [last]
+        frames, ins = make_burst(0xBA5E + base + last, lengths)
+        buf, off = _pack(frames)
+        whole = torch.full((base + buf.size,), 0xA5, dtype=torch.uint8, device="cuda:0")
+        whole[base:] = torch.from_numpy(buf).cuda()
+        d = whole[base:]
+        assert d.data_ptr() % 4 == base
+        check_hop(eng, routes, neigh, router, rneigh, frames, ins, d, len(frames), (base, last), offsets=_t(off))
+        w = whole.cpu().numpy()
+        assert (w[:base] == 0xA5).all() and (w[base:] == buf).all()  # the frames are only read
+    # fixed stride from the same bases
+    frames, ins = make_burst(0xBA5E0 + base, [60] * 130)
+    buf = np.frombuffer(b"".join(frames), np.uint8)
+    whole = torch.full((base + buf.size,), 0xA5, dtype=torch.uint8, device="cuda:0")
+    whole[base:] = torch.from_numpy(buf.copy()).cuda()
+    check_hop(eng, routes, neigh, router, rneigh, frames, ins, whole[base:], 130, base, stride=60, frame_len=60)
+
+
+def test_absent_outputs_null_tables_and_empty_batches(hop):
+    import torch
+
+    eng, routes, neigh, router, rneigh = hop
+    n = 40
+    frames, ins = make_burst(0xAB5, [60] * n)
+    buf = np.frombuffer(b"".join(frames), np.uint8)
+    want_st, want_f, want_h, want_rec = expect(frames, ins, router, rneigh)
+    d, dins = _t(buf), _t(ins)
+    lib, stream = eng.lib, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for with_f, with_h in ((True, False), (False, True), (False, False)):
+        hd, st = _sentinel(n * 36, torch.uint8, 0xA5), _sentinel(n, torch.uint8, 0x5A)
+        f, h = _sentinel(n, torch.int32, 0x25A5A5A5), _sentinel(n, torch.int32, 0x25A5A5A5)
+        eng._check(lib.ics_router_frames(eng.ctx, routes.handle, neigh.handle, d.data_ptr(), None, 60, 60, n, 0,
+                                         dins.data_ptr(), hd.data_ptr(), st.data_ptr(),
+                                         f.data_ptr() if with_f else None, h.data_ptr() if with_h else None, stream))
+        assert (st.cpu().numpy() == want_st).all() and (hd.cpu().numpy().reshape(n, 36) == want_rec).all()
+        assert (_u32(f) == (want_f if with_f else 0x25A5A5A5)).all()
+        assert (_u32(h) == (want_h if with_h else 0x25A5A5A5)).all()
+    before = eng.dispatch_info()["kernel"]
+    assert lib.ics_router_frames(eng.ctx, routes.handle, neigh.handle, None, None, 60, 60, 0, 0, None, None, None,
+                                 None, None, stream) == 0
+    assert lib.ics_frame_recv_batch(eng.ctx, neigh.handle, None, None, 60, 60, 0, 0, None, None, stream) == 0
+    assert eng.dispatch_info()["kernel"] == before  # n == 0 launches nothing
+    st = _sentinel(n, torch.uint8, 0x5A)
+    hd = _sentinel(n * 36, torch.uint8, 0xA5)
+    assert lib.ics_frame_recv_batch(eng.ctx, None, d.data_ptr(), None, 60, 60, n, 0, None, st.data_ptr(),
+                                    stream) == -1
+    assert b"null neighbour table" in lib.ics_last_error()
+    assert lib.ics_router_frames(eng.ctx, routes.handle, None, d.data_ptr(), None, 60, 60, n, 0, None, hd.data_ptr(),
+                                 st.data_ptr(), None, None, stream) == -1
+    assert b"null neighbour table" in lib.ics_last_error()
+    assert lib.ics_router_frames(eng.ctx, None, neigh.handle, d.data_ptr(), None, 60, 60, n, 0, None, hd.data_ptr(),
+                                 st.data_ptr(), None, None, stream) == -1
+    assert b"null route table" in lib.ics_last_error()
+    assert lib.ics_router_frames(eng.ctx, routes.handle, neigh.handle, d.data_ptr(), None, 60, 60, n, 0, None, None,
+                                 st.data_ptr(), None, None, stream) == -1
+    assert lib.ics_router_frames(eng.ctx, routes.handle, neigh.handle, d.data_ptr(), None, 60, 60, n, 0, None,
+                                 hd.data_ptr() + 2, st.data_ptr(), None, None, stream) == -1
+    assert (st.cpu().numpy() == 0x5A).all() and (hd.cpu().numpy() == 0xA5).all()
+
+
+def _one(dst_ip, ttl=9):
+    p = bytearray(28)
+    p[0], p[3], p[8], p[9] = 0x45, 28, ttl, 17
+    p[16:20] = dst_ip.to_bytes(4, "big")
+    c = header_sum(p)
+    p[10], p[11] = c >> 8, c & 0xFF
+    return MACS[0] + bytes([2, 0, 0, 0, 0, 0x55]) + b"\x08\x00" + bytes(p)
+
+
+def test_table_changes_are_seen_by_the_next_call(hop):
+    """two calls on one stream around a change of the neighbour table: a learn, a changed address, a tick
+    past expiry, a new interface"""
+    from tcpip_network_protocol_stack_amd.engine import NeighTable
+
+    eng, routes, neigh0, router, _ = hop
+    t, ref = NeighTable(debug=neigh0.debug), RefNeigh()
+    for x in (t, ref):
+        x.set_iface(0, MACS[0], IPS[0])
+        x.set_iface(1, MACS[1], IPS[1])
+    frames = [_one(0x0A000114), _one(0xC0A807FE), _one(0x0A000007)]
+    ins = np.zeros(3, np.uint32)
+    buf, off = _pack(frames)
+    d, doff = _t(buf), _t(off)
+
+    def step(want_resolved):
+        st = check_hop(eng, routes, t, router, ref, frames, ins, d, 3, want_resolved, offsets=doff)
+        assert [bool(s & FR_RESOLVED) for s in st] == want_resolved
+
+    step([False, False, False])
+    for x in (t, ref):
+        x.learn(1, 0x0A000114, _nmac(1, 1))
+    step([True, False, False])
+    for x in (t, ref):
+        x.learn(1, 0x0A000114, _nmac(1, 2))  # the address changes: the record must carry the new one
+        x.tick(29999)
+    step([True, False, False])
+    for x in (t, ref):
+        x.learn(2, 0xC0A807FE, _nmac(2, 3))  # known, but interface 2 has no addresses yet
+        x.tick(2)
+    step([False, False, False])  # 30001 since the re-learn on 1: gone
+    for x in (t, ref):
+        x.set_iface(2, MACS[2], IPS[2])
+        x.learn(2, 0xC0A807FE, _nmac(2, 3))  # identical: only its timer restarts
+        x.learn(0, 0x0A000007, _nmac(0, 4))
+    step([False, True, True])
+    for x in (t, ref):
+        x.tick(30000)
+    step([False, True, True])  # exactly 30000: alive
+    for x in (t, ref):
+        x.tick(1, 0)
+    step([False, True, False])  # only interface 0 aged past the deadline
+    t.close()
+
+
+def test_more_tables_than_image_slots_and_wrapping_chains(hop):
+    """six neighbour tables through a context that keeps four images, one of them with hash chains that
+    wrap the end of its slot array; then the module's table again"""
+    from tcpip_network_protocol_stack_amd.engine import NeighTable
+
+    eng, routes, neigh0, router, rneigh0 = hop
+    rng = np.random.default_rng(0x51075)
+    frames = [_one(d) for d in DSTS] * 3
+    ins = np.zeros(len(frames), np.uint32)
+    buf, off = _pack(frames)
+    d, doff = _t(buf), _t(off)
+    tables, refs = [], []
+    for k in range(6):
+        t, ref = NeighTable(debug=neigh0.debug), RefNeigh()
+        for x in (t, ref):
+            for i in MACS:
+                x.set_iface(i, MACS[i], IPS[i])
+            for f, ip in NEIGH[k % 3:]:
+                x.learn(f, ip, _nmac(f, ip ^ k))
+        extra = int(rng.integers(0, 200)) if k != 2 else 0
+        if k == 2:  # every mapping of interface 1 crowds the last slot: the chain wraps to slot 0
+            nslots = slots_for(ref.stats()["mappings"] + 6)
+            crowd = [ip for ip in range(1, 200000) if neigh_hash(1, ip) & (nslots - 1) == nslots - 1][:6]
+            for x in (t, ref):
+                for ip in crowd:
+                    x.learn(1, ip, _nmac(1, ip))
+            assert t.stats()["image_slots"] == nslots
+            frames_k = [_one(0x0B000001)] + [_one(ip) for ip in crowd]
+        more = [int(ip) for ip in rng.integers(0, 2**32, extra)]
+        for x in (t, ref):
+            for ip in more:
+                x.learn(ip % 4, ip, _nmac(0, ip))
+        tables.append(t)
+        refs.append(ref)
+    # the crowded keys through a route that sends everything to interface 1 with the destination as next hop
+    from tcpip_network_protocol_stack_amd.engine import RouteTable
+
+    r1 = fill(RouteTable(debug=neigh0.debug), [(0, 0, 1, False, 0)])
+    b2, o2 = _pack(frames_k)
+    st = check_hop(eng, r1, tables[2], RefRouter([(0, 0, 1, False, 0)]), refs[2], frames_k, np.zeros(7, np.uint32),
+                   _t(b2), 7, "wrap", offsets=_t(o2))
+    assert [bool(s & FR_RESOLVED) for s in st] == [False] + [True] * 6
+    for k in [0, 1, 2, 3, 4, 5, 0, 2, 5, 1, 3, 3, 4]:
+        check_hop(eng, routes, tables[k], router, refs[k], frames, ins, d, len(frames), k, offsets=doff)
+    check_hop(eng, routes, neigh0, router, rneigh0, frames, ins, d, len(frames), "module table", offsets=doff)
+    r1.close()
+    for t in tables:
+        t.close()
