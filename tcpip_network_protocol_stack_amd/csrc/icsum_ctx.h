@@ -1,8 +1,9 @@
 // icsum_ctx.h — internal to libicsum.so: the engine context (struct ics_ctx,
-// opaque in include/icsum.h) and what the three translation units behind the
+// opaque in include/icsum.h) and what the four translation units behind the
 // C-ABI share:
 //   icsum_api.cpp       argument validation, device binding, error strings, the extern "C" entry points
 //   icsum_dispatch.cpp  device-buffer dispatch: geometry choice, the plan cache, binning, multi-batch grouping
+//   icsum_images.cpp    the route and neighbour images' device residency and the launches that read them
 //   icsum_host.cpp      the host-memory (PCIe-inclusive) pipeline and its staging slots
 // Not installed, not part of the ABI.
 #pragma once
@@ -80,7 +81,7 @@ struct ics_ctx {
   uint64_t bin_min = uint64_t(1) << 16;
   uint32_t bin_blocks = 2048;    // grid of the bins 0-3 launch (their sizes are only known on the device)
   uint32_t last_bin_blocks = 0;  // grid cap of the last bin's launch (0: one lane group per segment)
-  uint32_t last_bin_lps = 0;     // lanes per segment of the last bin's launch (0: auto, see checksum_device)
+  uint32_t last_bin_lps = 0;     // lanes per segment of the last bin's launch (0: auto, see choose_checksum)
   int dense_segs = 4;            // k_checksum_dense segments per lane group in flight (0: off)
   int bin_plan = -1;  // -1: decided on the device per batch; forced: 0 whole, 1 split, 2 whole16, 3 wholeS
   int twoclass = 0;   // 0: auto; 16 / 32: every offsets batch through the two-class launch (that many per wave)
@@ -248,6 +249,8 @@ struct ics_ctx {
     uint64_t id = 0, gen = 0;  // id 0: empty
     uint32_t* d = nullptr;
     size_t cap = 0;  // bytes
+    // a route image: its trie words and route records; a neighbour image
+    // (csrc/icsum_neigh.h): its identity entries and hash slots
     uint64_t nwords = 0;
     uint32_t nrecs = 0;
     uint64_t used = 0;        // LRU clock
@@ -256,8 +259,7 @@ struct ics_ctx {
   };
   RouteSlot route_slot[kRouteSlots];
   // neighbour images (ics_frame_recv_batch, ics_router_frames), kept the same
-  // way under the same lock: nwords holds the identity entries, nrecs the
-  // hash slots of the image (csrc/icsum_neigh.h)
+  // way under the same lock
   RouteSlot neigh_slot[kRouteSlots];
   uint64_t route_clock = 0;
   std::vector<void*> route_retired;
@@ -320,6 +322,18 @@ class Scratch {
 
 // ICSUM_FORCE: parse "key=value,..." into ctx's test hooks.
 int apply_force(ics_ctx* ctx, const char* spec);
+// Does a test hook force the per-segment kernels' geometry?
+inline bool forced_geometry(const ics_ctx* ctx) {
+  return ctx->force_lps || ctx->force_unroll || ctx->force_mode >= 0 || ctx->force_segs;
+}
+// diagnostics: the last call's main launch (ics_dispatch_info; include/icsum.h
+// has what lps / unroll hold for each ICS_K_*) — the one writer of the last_* fields
+inline void report_launch(ics_ctx* ctx, int kernel, int lps = 0, int unroll = 0, int plan = -1) {
+  ctx->last_kernel.store(kernel, std::memory_order_relaxed);
+  ctx->last_lps.store(lps, std::memory_order_relaxed);
+  ctx->last_unroll.store(unroll, std::memory_order_relaxed);
+  ctx->last_plan.store(plan, std::memory_order_relaxed);
+}
 // The geometry of a batch whose mean length is avg_len (test hooks applied).
 icsum::Geometry geometry_for(const ics_ctx* ctx, uint64_t avg_len);
 // The fused IPv4 kernels' variant of a checksum geometry.
@@ -340,6 +354,11 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
 // c2: the router's TTL decrement + header checksum recompute, in place
 // (d_hdrs null) or with the forwarded headers to d_hdrs (20 bytes each).
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st);
+// Multi-batch calls: batches grouped by kernel shape, one launch per group.
+int checksum_batchv_device(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, hipStream_t st);
+int ipv4_batchv_device(ics_ctx* ctx, const ics_dgram_batch* batches, uint32_t k, int mode, hipStream_t st);
+
+// ---- icsum_images.cpp: the route and neighbour images on the device.
 // Router::match on the device: sp null = the lookup-only batch over d_addrs
 // (n addresses), else the router step of `sp` with the lookup fused (d_hdrs
 // as router_device).  Brings the table's image up to date on `st` first.
@@ -353,9 +372,6 @@ int frames_device(ics_ctx* ctx, ics_route_table* routes, ics_neigh_table* neigh,
                   uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st);
 // Release the route and neighbour images (ics_destroy).
 void free_routes(ics_ctx* ctx);
-// Multi-batch calls: batches grouped by kernel shape, one launch per group.
-int checksum_batchv_device(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, hipStream_t st);
-int ipv4_batchv_device(ics_ctx* ctx, const ics_dgram_batch* batches, uint32_t k, int mode, hipStream_t st);
 
 // ---- icsum_host.cpp: the host-memory pipeline.
 // kind 0: checksum batch (u16 out); kind 1: ipv4_tcp batch (ip u16, tcp u16, status u8);

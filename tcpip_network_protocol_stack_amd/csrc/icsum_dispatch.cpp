@@ -1,15 +1,17 @@
 // icsum_dispatch.cpp — device-buffer dispatch behind the C-ABI (icsum_api.cpp):
 // which kernel and geometry runs a batch, the plan cache that remembers the
 // device's view of an offsets batch's length mix, the binned launches, the
-// device wrap's one- or two-pass choice and the multi-batch grouping.  All
-// arithmetic happens in the HIP kernels (kernels/icsum_kernels.hip and its family headers).
+// device wrap's one- or two-pass choice and the multi-batch grouping.  Each
+// single-batch path (checksum, fused IPv4, wrap) is one plan read
+// (plan_lookup), one pure choice (choose_*: a Launch by value) and one issuer
+// (issue_*: the launches, the re-plan behind them, ics_dispatch_info's
+// fields).  All arithmetic happens in the HIP kernels
+// (kernels/icsum_kernels.hip and its family headers).
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "icsum_ctx.h"
-#include "icsum_neigh.h"
-#include "icsum_route.h"
 
 namespace icsum::detail {
 
@@ -17,6 +19,11 @@ static_assert(icsum::kBvDense64 == ICS_BV_DENSE64 && icsum::kBvTiny == ICS_BV_TI
                   icsum::kBvLine16 == ICS_BV_LINE16 && icsum::kBvLine64 == ICS_BV_LINE64 &&
                   icsum::kBvLane1 == ICS_BV_LANE1,
               "multi-batch shapes are reported as ICS_BV_*");
+
+// the geometries the dispatch names itself (the others come from pick_geometry)
+constexpr icsum::Geometry kLine16x8{16, 8, true, 3, 1};  // the 16-lane line grid of MTU-sized segments
+constexpr icsum::Geometry kLine8x8{8, 8, true, 3, 1};    // 8-lane groups
+constexpr icsum::Geometry kLane1{1, 4, false, 0, 1};     // fused kernels: one lane per datagram, default-policy loads
 
 // Segments per k_span wave: the forced value; with the cached plan's mean
 // length (capped at 4095 by the plan), about ics_ctx::kSpanBytes of segments
@@ -53,7 +60,7 @@ icsum::Geometry geometry_for(const ics_ctx* ctx, uint64_t avg_len) {
 icsum::Geometry ipv4_geometry(icsum::Geometry g) {
   g.segs = 1;
   if (g.mode == icsum::kModeTiny) g = {4, 1, true, 2, 1};  // the tiny kernel is checksum-only
-  if (!icsum::geometry_supported(g)) g = {16, 8, true, 3, 1};
+  if (!icsum::geometry_supported(g)) g = kLine16x8;
   return g;
 }
 
@@ -64,8 +71,7 @@ icsum::Geometry ipv4_geometry(icsum::Geometry g) {
 // 20.68 / 16.58 us (profiles/r4_ab_ipv4_unroll7.jsonl).  The plain checksum
 // keeps 8 (already 8 waves; 1 M x 1500 B 209.2 vs 211.2 us at 7).
 icsum::Geometry ipv4_fixed_geometry(const ics_ctx* ctx, icsum::Geometry g, uint64_t len) {
-  const bool forced = ctx->force_lps || ctx->force_unroll || ctx->force_mode >= 0 || ctx->force_segs;
-  if (!forced && g.lps == 16 && g.unroll == 8 && g.mode == 3 && len > 0 && len <= 1664) g.unroll = 7;
+  if (!forced_geometry(ctx) && g.lps == 16 && g.unroll == 8 && g.mode == 3 && len > 0 && len <= 1664) g.unroll = 7;
   return g;
 }
 
@@ -74,18 +80,6 @@ namespace {
 // average segment length for the geometry choice without reading d_offsets
 uint64_t avg_len_hint(const uint64_t* offsets, uint64_t seg_len) {
   return offsets ? 65536 : seg_len;  // unknown mix: the long-segment geometry
-}
-
-bool forced_geometry(const ics_ctx* ctx) {
-  return ctx->force_lps || ctx->force_unroll || ctx->force_mode >= 0 || ctx->force_segs;
-}
-
-// diagnostics: the last call's main launch (ics_dispatch_info)
-void note(ics_ctx* ctx, int kernel, icsum::Geometry g = {0, 0, true, 0, 1}, int plan = -1) {
-  ctx->last_kernel.store(kernel, std::memory_order_relaxed);
-  ctx->last_lps.store(g.lps, std::memory_order_relaxed);
-  ctx->last_unroll.store(g.unroll, std::memory_order_relaxed);
-  ctx->last_plan.store(plan, std::memory_order_relaxed);
 }
 
 int kernel_of(icsum::Geometry g) {
@@ -100,13 +94,15 @@ int kernel_of(icsum::Geometry g) {
 // The plan cache (ics_ctx::plan_slot): a lookup finds the slot keyed by this
 // batch's (offsets pointer, n) and trusts its word only when the word carries
 // the slot's generation — i.e. it was written by a plan kernel this key's
-// miss (or refresh) queued, and has landed.  any_plan = false accepts only
-// the whole-batch plans.  The mix receives the shares k_bin_plan reported, in
-// sixteenths: segments of <= 144 bytes, and bytes in segments over 1920
-// bytes.  A miss (re)keys the least recently used slot; *want_plan asks the
-// caller to queue the plan kernels (into *plan_dst, with *plan_gen) behind its
-// launch: on a miss, on every kPlanRefresh-th hit, and every kPlanRefresh-th
-// lookup of a key whose plan has not landed yet.
+// miss (or refresh) queued, and has landed.  The mix holds the shares
+// k_bin_plan reported, in sixteenths: segments of <= 144 bytes, and bytes in
+// segments over 1920 bytes.  A miss (re)keys the least recently used slot;
+// req.want asks the issuer to queue the plan kernels (into req.dst, with
+// req.gen) behind its launch: on a miss, on every kPlanRefresh-th hit, and
+// every kPlanRefresh-th lookup of a key whose plan has not landed yet.  Each
+// entry path reads the cache once, under its own conditions; all need an
+// offsets batch of kSmallPlanMin..2^32 - 1 segments (the word holds n's low
+// 32 bits).
 struct PlanMix {
   uint32_t short16 = 0, long16 = 0, avg = 0;  // avg: mean segment length, bytes (capped at 4095)
 };
@@ -115,10 +111,15 @@ struct PlanReq {
   uint64_t* dst = nullptr;  // device view of the slot's word
   uint32_t gen = 0;
 };
-bool plan_lookup(ics_ctx* ctx, const icsum::SegSpec& sp, bool any_plan, uint32_t* plan, PlanReq* req,
-                 PlanMix* mix = nullptr) {
-  *req = {};
-  if (!ctx->plan_host) return false;
+struct PlanRead {
+  bool hit = false;
+  uint32_t plan = 0;  // icsum::kPlan* of a hit
+  PlanMix mix;        // of a hit (zero on a miss)
+  PlanReq req;
+};
+PlanRead plan_lookup(ics_ctx* ctx, const icsum::SegSpec& sp) {
+  PlanRead r;
+  if (!ctx->plan_host) return r;
   std::lock_guard<std::mutex> lock(ctx->plan_mu);
   int k = -1, lru = 0;
   for (int i = 0; i < ics_ctx::kPlanSlots; ++i) {
@@ -130,38 +131,65 @@ bool plan_lookup(ics_ctx* ctx, const icsum::SegSpec& sp, bool any_plan, uint32_t
     ics_ctx::PlanSlot& ps = ctx->plan_slot[k];
     ps.used = ++ctx->plan_clock;
     const uint64_t v = __atomic_load_n(ctx->plan_host + k, __ATOMIC_ACQUIRE);
-    const uint32_t p = uint32_t(v & 0xfu);
-    const bool landed = (v >> 56) == ps.gen && ((v >> 8) & 0xFFFFFFFFull) == (sp.n & 0xFFFFFFFFull);
-    const bool whole = p == icsum::kPlanWholeBatch || p == icsum::kPlanWholeBatch16 || p == icsum::kPlanWholeBatchSmall;
     const bool again = ++ps.hits % ics_ctx::kPlanRefresh == 0;
-    *req = {again, ctx->plan_host_dev + k, ps.gen};
-    if (landed && (whole || any_plan)) {
-      if (mix) *mix = {uint32_t(v >> 4) & 0xfu, uint32_t(v >> 40) & 0xfu, uint32_t(v >> 44) & 0xfffu};
-      *plan = p;
-      ctx->n_hits.fetch_add(1, std::memory_order_relaxed);
-      return true;
+    r.req = {again, ctx->plan_host_dev + k, ps.gen};
+    r.hit = (v >> 56) == ps.gen && ((v >> 8) & 0xFFFFFFFFull) == (sp.n & 0xFFFFFFFFull);  // the word has landed
+    if (r.hit) {
+      r.plan = uint32_t(v & 0xfu);
+      r.mix = {uint32_t(v >> 4) & 0xfu, uint32_t(v >> 40) & 0xfu, uint32_t(v >> 44) & 0xfffu};
     }
-    ctx->n_misses.fetch_add(1, std::memory_order_relaxed);
-    return false;
+    (r.hit ? ctx->n_hits : ctx->n_misses).fetch_add(1, std::memory_order_relaxed);
+    return r;
   }
   ics_ctx::PlanSlot& ps = ctx->plan_slot[lru];
   ctx->plan_gen = ctx->plan_gen % 254 + 1;  // 1..254: never the 0xFF of an unwritten word
   ps = {sp.offsets, sp.n, ctx->plan_gen, 0, ++ctx->plan_clock};
   __atomic_store_n(ctx->plan_host + lru, ~uint64_t(0), __ATOMIC_RELEASE);
-  *req = {true, ctx->plan_host_dev + lru, ps.gen};
+  r.req = {true, ctx->plan_host_dev + lru, ps.gen};
   ctx->n_misses.fetch_add(1, std::memory_order_relaxed);
-  return false;
+  return r;
 }
+bool plan_sized(const icsum::SegSpec& sp) {
+  return sp.offsets && sp.n >= ics_ctx::kSmallPlanMin && sp.n <= 0xFFFFFFFFull;
+}
+
+constexpr size_t kMetaBytes = (icsum::kBinMetaBytesTotal + 255) & ~size_t(255);
 
 // stats + plan kernels only (no lists) behind a launch: the plan for the next
 // call with the same offsets lands in the slot plan_lookup named
 int replan(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t lps, const PlanReq& req, hipStream_t st) {
   if (!req.want) return ICS_OK;
-  Scratch meta(ctx, (icsum::kBinMetaBytesTotal + 255) & ~size_t(255), st);
+  Scratch meta(ctx, kMetaBytes, st);
   ICS_HIP(meta.error());
   ICS_HIP(icsum::launch_bin_plan(sp.offsets, sp.n, static_cast<uint32_t*>(meta.get()), lps, req.dst, req.gen, st));
   ctx->n_replans.fetch_add(1, std::memory_order_relaxed);
   return ICS_OK;
+}
+
+// What a chooser decided, by value.  The issuers turn it into the launches
+// and, through note, into ics_dispatch_info's last_* fields.
+struct Launch {
+  int kernel = 0;             // ICS_K_*
+  icsum::Geometry g{};        // the per-segment launch; of a two-class or dense launch, the launch
+                              // that runs when that launcher refuses the batch (lps 0: none)
+  int plan = -1;              // the cached plan to report (-1: none)
+  uint32_t max_blocks = 0;    // grid cap of the per-segment launch (0: one lane group per segment)
+  uint32_t span = 0;          // ICS_K_TILE: segments per wave
+  int tile_op = 0;            // ICS_K_TILE: ICS_TILE_*
+  int spw = 0;                // two-class launches: segments per wave
+  uint32_t plan_lps = 64;     // the re-plan's last_lps: the last bin's lanes in the plan kernel's cost model
+};
+Launch tile_launch(uint32_t span, int op, int plan) { return {ICS_K_TILE, {}, plan, 0, span, op}; }
+Launch two_class(int kernel, int spw, icsum::Geometry fallback, int plan) { return {kernel, fallback, plan, 0, 0, 0, spw}; }
+
+void note(ics_ctx* ctx, const icsum::SegSpec& sp, const Launch& L) {
+  switch (L.kernel) {
+    case ICS_K_TILE: return report_launch(ctx, L.kernel, int(L.span), L.tile_op, L.plan);
+    case ICS_K_TWOCLASS:
+    case ICS_K_IPV4_TWOCLASS: return report_launch(ctx, L.kernel, 16, L.spw, L.plan);  // the long segments' lanes
+    case ICS_K_DENSE: return report_launch(ctx, L.kernel, int(sp.seg_len / 16), ctx->dense_segs, L.plan);
+    default: return report_launch(ctx, L.kernel, L.g.lps, L.g.unroll, L.plan);
+  }
 }
 
 // a batch of many short segments with (almost) no bytes in long ones: from
@@ -169,7 +197,7 @@ int replan(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t lps, const PlanReq& 
 // in segments over 1920 bytes, one launch beats the binned launches and
 // 16-lane groups — first 8-lane groups (1 M datagrams, 50 % / 75 % 40-byte
 // ACKs + 1500 B: 139.5 / 107.4 us vs 146.0 / 125.6 us AUTO;
-// profiles/r2_csum_mix_sweep.jsonl), now the two-class launch (launch_mix)
+// profiles/r2_csum_mix_sweep.jsonl), now the two-class launch (mix_launch)
 bool short_mix(const PlanMix& m) { return m.short16 >= ics_ctx::kShortMix16 && m.long16 == 0; }
 
 // The tile launch (k_span) for an offsets batch whose device-reported mix
@@ -177,7 +205,7 @@ bool short_mix(const PlanMix& m) { return m.short16 >= ics_ctx::kShortMix16 && m
 // bytes (variable lengths leave per-segment lane groups idle), or — for the
 // wraps, which have no length binning — a sixteenth or more of the bytes in
 // segments over 1920 bytes; the fused IPv4 kernel on every mix but the
-// short-heavy ones (ipv4_device).  Short-heavy mixes keep the two-class
+// short-heavy ones (choose_ipv4).  Short-heavy mixes keep the two-class
 // launches (checked first by the callers), MTU-sized means the 16-lane line
 // grid.  tools/ab_stream.py, profiles/r5l_ab_span_vs_per_segment.jsonl,
 // r5m_ab_c4.jsonl, r5p_ab_span_thresholds.jsonl (us back to back,
@@ -204,18 +232,8 @@ bool tile_wins(const ics_ctx* ctx, const PlanMix& m, uint64_t n, bool fused) {
 // plain rows, 64 / 32 / 16): 7/8 ACKs 43.5 / 42.2 / 54.5, 3/4 74.8 / 68.5 /
 // 74.5, 1/2 132.4 / 122.5 / 119.0, 7/16 145.0 / 139.3 / 131.9 us
 // (profiles/r2_twoclass_spw*.jsonl).  Batches past the two-class grid's
-// limit run 8-lane groups.
-hipError_t launch_mix(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_init, const uint8_t* d_odd,
-                      void* d_out, int out_kind, const PlanMix& mix, hipStream_t st) {
-  const int spw = mix.short16 >= 12 ? 32 : 16;
-  const hipError_t e = icsum::launch_checksum_twoclass(sp, d_init, d_odd, d_out, out_kind, spw, ctx->twoclass_remap, st, ctx->twoclass_lds);
-  if (e != hipErrorInvalidValue) {
-    note(ctx, ICS_K_TWOCLASS, {16, spw, true, 3, 1});
-    return e;
-  }
-  note(ctx, ICS_K_CHECKSUM, {8, 8, true, 3, 1});
-  return icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, icsum::Geometry{8, 8, true, 3, 1}, 0, st);
-}
+// limit run 8-lane groups.  It reports no plan.
+Launch mix_launch(const PlanMix& mix) { return two_class(ICS_K_TWOCLASS, mix.short16 >= 12 ? 32 : 16, kLine8x8, -1); }
 
 // the small-segment plan's single launch: one lane per segment for ACK-sized
 // means (icsum::kTinyMaxAvg), else 4-lane groups with 2 segments in flight
@@ -224,59 +242,27 @@ icsum::Geometry small_plan_geometry(const PlanMix& m) {
                                      : icsum::Geometry{4, 2, true, 2, 2};
 }
 
-}  // namespace
-
-int checksum_device(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_init, const uint8_t* d_odd,
-                    void* d_out, int out_kind, hipStream_t st) {
-  if (sp.offsets && ctx->twoclass) {  // test hook: the two-class launch on every offsets batch
-    ICS_HIP(icsum::launch_checksum_twoclass(sp, d_init, d_odd, d_out, out_kind, ctx->twoclass, ctx->twoclass_remap, st, ctx->twoclass_lds));
-    note(ctx, ICS_K_TWOCLASS, {16, ctx->twoclass, true, 3, 1});
-    return ICS_OK;
-  }
-  if (sp.offsets && ctx->tile == 1) {  // test hook: the tile launch on every offsets batch
-    const uint32_t S = span_segs_for(ctx, 0);
-    ICS_HIP(icsum::launch_tile_checksum(sp, d_init, d_odd, d_out, out_kind, S, st, ctx->span_blocks));
-    note(ctx, ICS_K_TILE, {int(S), ICS_TILE_CHECKSUM, true, 0, 1});
-    return ICS_OK;
-  }
-  const bool binned = sp.offsets && sp.n <= 0xFFFFFFFFull &&
-                      (ctx->bin == 1 || (ctx->bin < 0 && sp.n >= ctx->bin_min && !forced_geometry(ctx)));
-  const bool plannable = ctx->bin < 0 && ctx->bin_plan < 0 && ctx->plan_host && sp.n <= 0xFFFFFFFFull;
-  if (!binned && sp.offsets && plannable && !forced_geometry(ctx) && sp.n >= ics_ctx::kSmallPlanMin) {
+// ---- checksum (a1-a4).  parity: the call carries a parity array (no dense kernel)
+Launch choose_checksum(const ics_ctx* ctx, const icsum::SegSpec& sp, bool parity, bool binned, const PlanRead& pr) {
+  if (sp.offsets && ctx->twoclass)  // test hook: the two-class launch on every offsets batch
+    return two_class(ICS_K_TWOCLASS, ctx->twoclass, {}, -1);
+  if (sp.offsets && ctx->tile == 1)  // test hook: the tile launch on every offsets batch
+    return tile_launch(span_segs_for(ctx, 0), ICS_TILE_CHECKSUM, -1);
+  const bool wholeS = pr.hit && pr.plan == icsum::kPlanWholeBatchSmall;
+  const bool mix8 = pr.hit && !wholeS && short_mix(pr.mix);
+  if (!binned) {
+    if (mix8) return mix_launch(pr.mix);
+    icsum::Geometry g = geometry_for(ctx, avg_len_hint(sp.offsets, sp.seg_len));
+    // dense fixed-stride batch of short segments (config 3): the flat-array kernel
+    if (!parity && ctx->dense_segs > 0 && !forced_geometry(ctx) && icsum::dense_supported(sp)) return {ICS_K_DENSE, g};
     // an offsets batch below the binning threshold: one launch, its geometry
     // from the plan the device reported for this batch last time (16-lane
     // groups for MTU-sized mixes, the small-segment body for short ones);
     // on a miss the unknown-mix geometry, and the plan kernels run behind
     // the launch for the next call (git 7692616:tools/ab_small_offsets.py)
-    uint32_t plan = 0;
-    PlanMix mix;
-    PlanReq req;
-    const bool hit = plan_lookup(ctx, sp, true, &plan, &req, &mix);
-    icsum::Geometry g = geometry_for(ctx, avg_len_hint(sp.offsets, sp.seg_len));
-    if (hit && plan == icsum::kPlanWholeBatch16) g = {16, 8, true, 3, 1};
-    if (hit && plan == icsum::kPlanWholeBatchSmall) g = small_plan_geometry(mix);
-    if (hit && plan != icsum::kPlanWholeBatchSmall && short_mix(mix)) {
-      ICS_HIP(launch_mix(ctx, sp, d_init, d_odd, d_out, out_kind, mix, st));
-    } else {
-      ICS_HIP(icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, g, 0, st));
-      note(ctx, kernel_of(g), g, hit ? int(plan) : -1);
-    }
-    return replan(ctx, sp, 64, req, st);
-  }
-  if (!binned) {
-    // dense fixed-stride batch of short segments (config 3): the flat-array kernel
-    if (!d_odd && ctx->dense_segs > 0 && !forced_geometry(ctx) && icsum::dense_supported(sp)) {
-      const hipError_t e = icsum::launch_checksum_dense(sp, d_init, d_out, out_kind, ctx->dense_segs, st);
-      if (e != hipErrorInvalidValue) {
-        ICS_HIP(e);
-        note(ctx, ICS_K_DENSE, {int(sp.seg_len / 16), ctx->dense_segs, true, 0, 1});
-        return ICS_OK;
-      }
-    }
-    const icsum::Geometry g = geometry_for(ctx, avg_len_hint(sp.offsets, sp.seg_len));
-    ICS_HIP(icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, g, 0, st));
-    note(ctx, kernel_of(g), g);
-    return ICS_OK;
+    if (pr.hit && pr.plan == icsum::kPlanWholeBatch16) g = kLine16x8;
+    if (wholeS) g = small_plan_geometry(pr.mix);
+    return {kernel_of(g), g, pr.hit ? int(pr.plan) : -1};
   }
   // the whole-batch plan's launch geometry: one lane group per segment of the
   // batch; above 1 M segments 32-lane groups halve the waves an empty last bin
@@ -284,47 +270,39 @@ int checksum_device(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_in
   icsum::Geometry g_last = icsum::bin_geometry(icsum::kBins - 1);
   const uint32_t lps = ctx->last_bin_lps ? ctx->last_bin_lps : (sp.n > (uint64_t(1) << 20) ? 32u : 64u);
   if (lps == 32) g_last = {32, 8, true, 3, 1};
-  PlanReq req;
-  if (plannable) {
-    uint32_t hit_plan = 0;
-    PlanMix mix;
-    const bool hit = plan_lookup(ctx, sp, true, &hit_plan, &req, &mix);
-    const bool mix8 = hit && hit_plan != icsum::kPlanWholeBatchSmall && short_mix(mix);
-    if (hit && !mix8 && hit_plan != icsum::kPlanWholeBatchSmall && tile_wins(ctx, mix, sp.n, false)) {
-      const uint32_t S = span_segs_for(ctx, mix.avg);
-      ICS_HIP(icsum::launch_tile_checksum(sp, d_init, d_odd, d_out, out_kind, S, st, ctx->span_blocks));
-      note(ctx, ICS_K_TILE, {int(S), ICS_TILE_CHECKSUM, true, 0, 1}, int(hit_plan));
-      return replan(ctx, sp, lps, req, st);
-    }
-    if (hit && (hit_plan != icsum::kPlanSplitBins || mix8)) {
-      // the whole-batch plan the device chose for this batch last time, as
-      // its single launch: the last bin's geometry (whole), 16-lane groups
-      // (whole16) or the small-segment body (wholeS) over every segment; a
-      // short-heavy mix with no long segments (received traffic: ACKs + MTU
-      // data) runs the two-class launch whatever the plan (launch_mix)
-      const icsum::Geometry g_hit = hit_plan == icsum::kPlanWholeBatch16      ? icsum::Geometry{16, 8, true, 3, 1}
-                                    : hit_plan == icsum::kPlanWholeBatchSmall ? small_plan_geometry(mix)
-                                                                              : g_last;
-      if (mix8) {
-        ICS_HIP(launch_mix(ctx, sp, d_init, d_odd, d_out, out_kind, mix, st));
-      } else {
-        ICS_HIP(icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, g_hit,
-                                       hit_plan == icsum::kPlanWholeBatch ? ctx->last_bin_blocks : 0, st));
-        note(ctx, kernel_of(g_hit), g_hit, int(hit_plan));
-      }
-      // re-plan behind it: a batch whose mix changed under the same pointer
-      // and size is re-binned from the next call on
-      return replan(ctx, sp, lps, req, st);
-    }
+  // the binning passes and the bin launches (issue_binned), under the forced plan if any
+  Launch L{ICS_K_BINNED, g_last, ctx->bin_plan, ctx->last_bin_blocks};
+  if (pr.hit && !mix8 && !wholeS && tile_wins(ctx, pr.mix, sp.n, false)) {
+    L = tile_launch(span_segs_for(ctx, pr.mix.avg), ICS_TILE_CHECKSUM, int(pr.plan));
+  } else if (mix8) {
+    L = mix_launch(pr.mix);
+  } else if (pr.hit && pr.plan != icsum::kPlanSplitBins) {
+    // the whole-batch plan the device chose for this batch last time, as
+    // its single launch: the last bin's geometry (whole), 16-lane groups
+    // (whole16) or the small-segment body (wholeS) over every segment; a
+    // short-heavy mix with no long segments (received traffic: ACKs + MTU
+    // data) runs the two-class launch whatever the plan (mix_launch)
+    const icsum::Geometry g_hit = pr.plan == icsum::kPlanWholeBatch16 ? kLine16x8
+                                  : wholeS                           ? small_plan_geometry(pr.mix)
+                                                                     : g_last;
+    L = {kernel_of(g_hit), g_hit, int(pr.plan), pr.plan == icsum::kPlanWholeBatch ? ctx->last_bin_blocks : 0};
   }
-  const size_t meta_bytes = (icsum::kBinMetaBytesTotal + 255) & ~size_t(255);
-  Scratch ws(ctx, meta_bytes + sp.n * 16 * icsum::kBins, st);
+  L.plan_lps = lps;
+  return L;
+}
+
+// The binned launches: a hit with the split plan that neither tiles nor is
+// short-heavy comes here too, and hands its re-plan request to the plan
+// kernel of the binning passes
+int issue_binned(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_init, const uint8_t* d_odd, void* d_out,
+                 int out_kind, const Launch& L, const PlanReq& req, hipStream_t st) {
+  Scratch ws(ctx, kMetaBytes + sp.n * 16 * icsum::kBins, st);
   ICS_HIP(ws.error());
   uint32_t* meta = static_cast<uint32_t*>(ws.get());
-  void* list = static_cast<uint8_t*>(ws.get()) + meta_bytes;
+  void* list = static_cast<uint8_t*>(ws.get()) + kMetaBytes;
   // the binning passes; the plan kernel also reports into the plan cache's
   // slot when this call's lookup asked for a plan
-  hipError_t e = icsum::launch_bin_segments(sp.offsets, sp.n, list, meta, ctx->bin_plan, lps,
+  hipError_t e = icsum::launch_bin_segments(sp.offsets, sp.n, list, meta, ctx->bin_plan, L.plan_lps,
                                             req.want ? req.dst : nullptr, req.gen, st);
   // bins 0..3: one launch, a capped grid striding over each bin; the last
   // bin: one lane group per segment of the batch (it takes the whole batch
@@ -334,17 +312,40 @@ int checksum_device(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_in
                                     ctx->bin_blocks, st);
   if (e == hipSuccess)
     e = icsum::launch_checksum(icsum::bin_spec(sp, list, meta, icsum::kBins - 1), d_init, d_odd, d_out, out_kind,
-                               g_last, ctx->last_bin_blocks, st);
+                               L.g, L.max_blocks, st);
   ICS_HIP(e);
   if (req.want) ctx->n_replans.fetch_add(1, std::memory_order_relaxed);
-  note(ctx, ICS_K_BINNED, g_last, ctx->bin_plan);
+  note(ctx, sp, L);
   return ICS_OK;
 }
 
-int ipv4_device(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip_ck, uint16_t* d_tcp_ck,
-                uint8_t* d_status, hipStream_t st) {
-  const uint64_t* d_offsets = sp.offsets;
-  const uint64_t n = sp.n;
+int issue_checksum(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_init, const uint8_t* d_odd, void* d_out,
+                   int out_kind, Launch L, const PlanReq& req, hipStream_t st) {
+  if (L.kernel == ICS_K_BINNED) return issue_binned(ctx, sp, d_init, d_odd, d_out, out_kind, L, req, st);
+  hipError_t e;
+  if (L.kernel == ICS_K_TWOCLASS)
+    e = icsum::launch_checksum_twoclass(sp, d_init, d_odd, d_out, out_kind, L.spw, ctx->twoclass_remap, st, ctx->twoclass_lds);
+  else if (L.kernel == ICS_K_DENSE)
+    e = icsum::launch_checksum_dense(sp, d_init, d_out, out_kind, ctx->dense_segs, st);
+  else if (L.kernel == ICS_K_TILE)
+    e = icsum::launch_tile_checksum(sp, d_init, d_odd, d_out, out_kind, L.span, st, ctx->span_blocks);
+  else
+    e = icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, L.g, L.max_blocks, st);
+  // a batch past the two-class grid's limit, a (seg_len, segs) the dense
+  // kernel is not instantiated for: the per-segment launch
+  if (e == hipErrorInvalidValue && (L.kernel == ICS_K_TWOCLASS || L.kernel == ICS_K_DENSE) && L.g.lps) {
+    L.kernel = kernel_of(L.g);
+    e = icsum::launch_checksum(sp, d_init, d_odd, d_out, out_kind, L.g, 0, st);
+  }
+  ICS_HIP(e);
+  note(ctx, sp, L);
+  // re-plan behind it: a batch whose mix changed under the same pointer
+  // and size is re-binned from the next call on
+  return replan(ctx, sp, L.plan_lps, req, st);
+}
+
+// ---- fused IPv4 + TCP (b1-b4)
+Launch choose_ipv4(const ics_ctx* ctx, const icsum::SegSpec& sp, const PlanRead& pr) {
   // an offsets batch of raw datagrams gives no length hint; datagrams are at
   // most 64 KiB and mostly MTU-sized, and the 16-lane line grid is the best
   // measured geometry for both 1500- and 9000-byte datagrams (64 Ki x 1500 B:
@@ -352,10 +353,9 @@ int ipv4_device(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip
   // ACK-sized datagrams (a fixed length <= kTinyMaxAvg, or a cached plan
   // whose mean is) run one lane per datagram with default-policy loads
   // (neighbours share lines): 1 M x 40 B VERIFY 30.3 -> 10.6 us (git 7692616:tools/ab_ipv4_mix.py, AB_LANE1)
-  const icsum::Geometry lane1{1, 4, false, 0, 1};
-  const icsum::Geometry base = geometry_for(ctx, d_offsets ? 1500 : sp.seg_len);
-  icsum::Geometry g = base.mode == icsum::kModeTiny ? lane1 : ipv4_geometry(base);
-  if (!d_offsets) g = ipv4_fixed_geometry(ctx, g, sp.seg_len);
+  const icsum::Geometry base = geometry_for(ctx, sp.offsets ? 1500 : sp.seg_len);
+  icsum::Geometry g = base.mode == icsum::kModeTiny ? kLane1 : ipv4_geometry(base);
+  if (!sp.offsets) g = ipv4_fixed_geometry(ctx, g, sp.seg_len);
   // a receive batch of mostly short datagrams (pure ACKs: 40 bytes) leaves
   // most of a 16-lane group idle: from 16 Ki datagrams up the geometry
   // follows the plan the device reported for the same offsets buffer last
@@ -363,76 +363,48 @@ int ipv4_device(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip
   // from 5/16 of <= 144-byte datagrams, 16 x 4 below that), the plan
   // kernels running behind the first and every 64th launch (DESIGN.md §4,
   // git 7692616:tools/ab_ipv4_mix.py, profiles/r2_ipv4_mix_sweep.jsonl)
-  bool two = false, tile = false;
-  uint32_t span_avg = 0;  // the cached plan's mean length (span_segs_for)
-  int spw = 16;
-  PlanReq req;
-  int plan_used = -1;
-  if (d_offsets && !forced_geometry(ctx) && !ctx->twoclass && n >= ics_ctx::kSmallPlanMin && n <= 0xFFFFFFFFull) {
-    uint32_t plan = 0;
-    PlanMix mix;
-    const bool hit = plan_lookup(ctx, sp, true, &plan, &req, &mix);
-    if (hit && plan == icsum::kPlanWholeBatchSmall && mix.avg <= icsum::kTinyMaxAvg)
-      g = lane1;
-    else if (hit && plan == icsum::kPlanWholeBatchSmall)
-      g = ipv4_geometry({4, 2, true, 2, 1});
-    else if (hit && mix.short16 >= ics_ctx::kIpv4ShortMix16 && mix.long16 == 0)
-      g = ipv4_geometry({8, 8, true, 3, 1});  // ACK + MTU mixes past the two-class grid's limit
-    else if (hit)
-      g = ipv4_geometry({16, 4, true, 3, 1});  // MTU + a few ACKs: shorter unroll, 1-4 % (1 M datagrams)
-    // the two-class launch (block lists, ics_ctx::kIpv4TwoClass16 for the
-    // crossover against 16 x 4 groups; round 2's per-wave version beat the
-    // 8-lane groups from 5/16 ACKs up, git 7692616:tools/ab_ipv4_mix.py)
-    two = hit && plan != icsum::kPlanWholeBatchSmall && mix.short16 >= ics_ctx::kIpv4TwoClass16 && mix.long16 == 0;
-    // ACK-heavy mixes: 128 datagrams per block, so the block's one short
-    // pass carries more of them (3/4 ACKs 78.4 -> 75.4 us, mix_probe blk32)
-    spw = mix.short16 >= ics_ctx::kIpv4TwoClassWide16 ? 32 : 16;
-    plan_used = hit ? int(plan) : -1;
-    tile = hit && !two && plan != icsum::kPlanWholeBatchSmall && ctx->tile != 0 && n >= ics_ctx::kTileMin;
-    span_avg = hit ? mix.avg : 0u;
-  }
-  if (d_offsets && ctx->twoclass) {  // test hook
-    two = true;
-    spw = ctx->twoclass;
-  }
-  if (d_offsets && (ctx->tile == 1 || tile)) {  // the test hook, or the cached mix favours the tile launch
-    const uint32_t S = span_segs_for(ctx, span_avg);
-    ICS_HIP(icsum::launch_tile_ipv4(sp, mode, d_ip_ck, d_tcp_ck, d_status, S, st, ctx->span_blocks));
-    note(ctx, ICS_K_TILE, {int(S), ICS_TILE_IPV4, true, 0, 1}, plan_used);
-    return replan(ctx, sp, 64, req, st);
-  }
-  hipError_t le = hipErrorInvalidValue;
-  if (two) {
-    le = icsum::launch_ipv4_twoclass(sp, mode, d_ip_ck, d_tcp_ck, d_status, spw, ctx->twoclass_remap, st, ctx->twoclass_lds);
-    if (le != hipErrorInvalidValue) note(ctx, ICS_K_IPV4_TWOCLASS, {16, spw, true, 3, 1}, plan_used);
-  }
-  if (le == hipErrorInvalidValue) {
-    le = icsum::launch_ipv4_tcp(sp, mode, d_ip_ck, d_tcp_ck, d_status, g, 0, st);
-    note(ctx, ICS_K_IPV4, g, plan_used);
-  }
-  ICS_HIP(le);
-  if (int rc = replan(ctx, sp, 64, req, st)) return rc;
-  return ICS_OK;
+  const PlanMix& mix = pr.mix;
+  const bool wholeS = pr.hit && pr.plan == icsum::kPlanWholeBatchSmall;
+  if (wholeS && mix.avg <= icsum::kTinyMaxAvg)
+    g = kLane1;
+  else if (wholeS)
+    g = ipv4_geometry({4, 2, true, 2, 1});
+  else if (pr.hit && mix.short16 >= ics_ctx::kIpv4ShortMix16 && mix.long16 == 0)
+    g = ipv4_geometry(kLine8x8);  // ACK + MTU mixes past the two-class grid's limit
+  else if (pr.hit)
+    g = ipv4_geometry({16, 4, true, 3, 1});  // MTU + a few ACKs: shorter unroll, 1-4 % (1 M datagrams)
+  // the two-class launch (block lists, ics_ctx::kIpv4TwoClass16 for the
+  // crossover against 16 x 4 groups; round 2's per-wave version beat the
+  // 8-lane groups from 5/16 ACKs up, git 7692616:tools/ab_ipv4_mix.py)
+  const bool two = pr.hit && !wholeS && mix.short16 >= ics_ctx::kIpv4TwoClass16 && mix.long16 == 0;
+  // ACK-heavy mixes: 128 datagrams per block, so the block's one short
+  // pass carries more of them (3/4 ACKs 78.4 -> 75.4 us, mix_probe blk32)
+  const int spw = mix.short16 >= ics_ctx::kIpv4TwoClassWide16 ? 32 : 16;
+  const int plan = pr.hit ? int(pr.plan) : -1;
+  const bool tile = pr.hit && !two && !wholeS && ctx->tile != 0 && sp.n >= ics_ctx::kTileMin;
+  if (sp.offsets && (ctx->tile == 1 || tile))  // the test hook, or the cached mix favours the tile launch
+    return tile_launch(span_segs_for(ctx, pr.hit ? mix.avg : 0u), ICS_TILE_IPV4, plan);
+  if (sp.offsets && ctx->twoclass) return two_class(ICS_K_IPV4_TWOCLASS, ctx->twoclass, g, plan);  // test hook
+  return two ? two_class(ICS_K_IPV4_TWOCLASS, spw, g, plan) : Launch{ICS_K_IPV4, g, plan};
 }
 
-namespace {
-// The device wrap: two passes (payload sums into n words of scratch, then the
-// header launch) or one (ics_ctx::wrap_passes)
-hipError_t device_wrap(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* msgs, uint32_t* hdr_out,
-                       uint16_t* ip_ck, uint16_t* tcp_ck, bool payload_only, icsum::Geometry g, int plan,
-                       hipStream_t st) {
-  const icsum::TcpMsg* m = reinterpret_cast<const icsum::TcpMsg*>(msgs);
-  if (!wrap_two_pass(ctx, hdr_out != nullptr, sp.n)) {
-    note(ctx, ICS_K_WRAP, g, plan);
-    return icsum::launch_tcp_wrap(sp, m, hdr_out, ip_ck, tcp_ck, payload_only, nullptr, g, 0, st);
+int issue_ipv4(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip_ck, uint16_t* d_tcp_ck,
+               uint8_t* d_status, Launch L, const PlanReq& req, hipStream_t st) {
+  hipError_t e = hipErrorInvalidValue;
+  if (L.kernel == ICS_K_TILE)
+    e = icsum::launch_tile_ipv4(sp, mode, d_ip_ck, d_tcp_ck, d_status, L.span, st, ctx->span_blocks);
+  else if (L.kernel == ICS_K_IPV4_TWOCLASS)
+    e = icsum::launch_ipv4_twoclass(sp, mode, d_ip_ck, d_tcp_ck, d_status, L.spw, ctx->twoclass_remap, st, ctx->twoclass_lds);
+  if (e == hipErrorInvalidValue && L.kernel != ICS_K_TILE) {  // no two-class launch, or past its grid's limit
+    L.kernel = ICS_K_IPV4;
+    e = icsum::launch_ipv4_tcp(sp, mode, d_ip_ck, d_tcp_ck, d_status, L.g, 0, st);
   }
-  Scratch sums(ctx, sp.n * 4, st);
-  if (sums.error() != hipSuccess) return sums.error();
-  note(ctx, ICS_K_WRAP_2PASS, g, plan);
-  return icsum::launch_tcp_wrap(sp, m, hdr_out, ip_ck, tcp_ck, payload_only, static_cast<uint32_t*>(sums.get()), g,
-                                0, st);
+  ICS_HIP(e);
+  note(ctx, sp, L);
+  return replan(ctx, sp, L.plan_lps, req, st);
 }
 
+// ---- the device wrap (c1)
 // The device wrap's geometry: one lane per datagram for ACK-sized batches (a
 // fixed length, or a cached small plan with a mean <= kTinyMaxAvg: 1 M pure
 // ACKs in place 78.3 -> 36.6 us, 40-56 B 119.0 -> 47.4 us,
@@ -440,33 +412,13 @@ hipError_t device_wrap(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg
 // hint.  The plan kernels run behind the launch as plan_lookup asks (the
 // wrap's transmit buffer keeps its own cache slot: a stack's receive-side
 // verify in between does not evict it).
-icsum::Geometry wrap_geometry(ics_ctx* ctx, const icsum::SegSpec& sp, uint64_t hint, PlanReq* req, int* plan_used,
-                              PlanMix* mix_out) {
-  const icsum::Geometry lane1{1, 4, false, 0, 1};
+Launch choose_wrap(const ics_ctx* ctx, const icsum::SegSpec& sp, bool headers_apart, bool payload_only, uint64_t hint,
+                   const PlanRead& pr) {
   const icsum::Geometry base = geometry_for(ctx, sp.offsets ? hint : sp.seg_len);
-  icsum::Geometry g = base.mode == icsum::kModeTiny ? lane1 : ipv4_geometry(base);
-  *req = {};
-  *plan_used = -1;
-  if (sp.offsets && !forced_geometry(ctx) && sp.n >= ics_ctx::kSmallPlanMin && sp.n <= 0xFFFFFFFFull) {
-    uint32_t plan = 0;
-    PlanMix mix;
-    const bool hit = plan_lookup(ctx, sp, true, &plan, req, &mix);
-    if (hit && plan == icsum::kPlanWholeBatchSmall && mix.avg <= icsum::kTinyMaxAvg) g = lane1;
-    if (hit) {
-      *plan_used = int(plan);
-      *mix_out = mix;
-    }
-  }
-  return g;
-}
-}  // namespace
-
-int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msgs, uint32_t* hdr_out,
-                uint16_t* d_ip_ck, uint16_t* d_tcp_ck, bool payload_only, uint64_t hint, hipStream_t st) {
-  PlanReq req;
-  int plan = -1;
-  PlanMix mix;
-  const icsum::Geometry g = wrap_geometry(ctx, sp, hint, &req, &plan, &mix);
+  icsum::Geometry g = base.mode == icsum::kModeTiny ? kLane1 : ipv4_geometry(base);
+  const bool wholeS = pr.hit && pr.plan == icsum::kPlanWholeBatchSmall;
+  if (wholeS && pr.mix.avg <= icsum::kTinyMaxAvg) g = kLane1;
+  const int plan = pr.hit ? int(pr.plan) : -1;
   // the tile launch: the test hook; headers apart when the cached mix favours
   // it; in place only for long-segment mixes (its header stores cost the
   // same scattered write per datagram either way, and the per-segment wrap
@@ -475,162 +427,73 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
   // mix of empty and MTU payloads tiles too (256 Ki / 1 M: 48.8 / 40.5 and
   // 169.3 / 150.8 us), payloads nearly all empty (pure ACKs) do not (1 M:
   // 24.2 / 41.0 us; profiles/r4_ab_dispatch_tile.jsonl)
-  const bool tile_pick = plan >= 0 && plan != int(icsum::kPlanWholeBatchSmall) &&
+  const PlanMix& mix = pr.mix;
+  const bool tile_pick = pr.hit && !wholeS &&
                          (payload_only ? mix.short16 < ics_ctx::kTileApartShort16 && tile_wins(ctx, mix, sp.n, true)
                                        : !short_mix(mix) && ctx->tile != 0 && sp.n >= ics_ctx::kTileMin &&
                                              mix.long16 >= 4);
-  if (sp.offsets && (ctx->tile == 1 || tile_pick)) {  // the wrap (in place or headers apart) as a tile launch
-    const uint32_t S = span_segs_for(ctx, plan >= 0 ? mix.avg : 0u);
-    ICS_HIP(icsum::launch_tile_wrap(sp, reinterpret_cast<const icsum::TcpMsg*>(d_msgs), hdr_out, d_ip_ck, d_tcp_ck,
-                                    S, st, ctx->span_blocks));
-    note(ctx, ICS_K_TILE, {int(S), hdr_out ? ICS_TILE_WRAP_APART : ICS_TILE_WRAP, true, 0, 1}, plan);
-    return replan(ctx, sp, 64, req, st);
+  if (sp.offsets && (ctx->tile == 1 || tile_pick))  // the wrap (in place or headers apart) as a tile launch
+    return tile_launch(span_segs_for(ctx, pr.hit ? mix.avg : 0u), headers_apart ? ICS_TILE_WRAP_APART : ICS_TILE_WRAP, plan);
+  // two passes (payload sums into n words of scratch, then the header launch) or one (ics_ctx::wrap_passes)
+  return {wrap_two_pass(ctx, headers_apart, sp.n) ? ICS_K_WRAP_2PASS : ICS_K_WRAP, g, plan};
+}
+
+int issue_wrap(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* msgs, uint32_t* hdr_out, uint16_t* d_ip_ck,
+               uint16_t* d_tcp_ck, bool payload_only, const Launch& L, const PlanReq& req, hipStream_t st) {
+  const icsum::TcpMsg* m = reinterpret_cast<const icsum::TcpMsg*>(msgs);
+  if (L.kernel == ICS_K_TILE) {
+    ICS_HIP(icsum::launch_tile_wrap(sp, m, hdr_out, d_ip_ck, d_tcp_ck, L.span, st, ctx->span_blocks));
+  } else if (L.kernel == ICS_K_WRAP) {
+    ICS_HIP(icsum::launch_tcp_wrap(sp, m, hdr_out, d_ip_ck, d_tcp_ck, payload_only, nullptr, L.g, 0, st));
+  } else {  // the scratch lease ends before the re-plan takes its own
+    Scratch sums(ctx, sp.n * 4, st);
+    ICS_HIP(sums.error());
+    ICS_HIP(icsum::launch_tcp_wrap(sp, m, hdr_out, d_ip_ck, d_tcp_ck, payload_only, static_cast<uint32_t*>(sums.get()),
+                                   L.g, 0, st));
   }
-  ICS_HIP(device_wrap(ctx, sp, d_msgs, hdr_out, d_ip_ck, d_tcp_ck, payload_only, g, plan, st));
-  return replan(ctx, sp, 64, req, st);
+  note(ctx, sp, L);
+  return replan(ctx, sp, L.plan_lps, req, st);
+}
+
+}  // namespace
+
+int checksum_device(ics_ctx* ctx, const icsum::SegSpec& sp, const uint32_t* d_init, const uint8_t* d_odd,
+                    void* d_out, int out_kind, hipStream_t st) {
+  const bool hooked = sp.offsets && (ctx->twoclass || ctx->tile == 1);  // choose_checksum's first two lines
+  const bool binned = sp.offsets && sp.n <= 0xFFFFFFFFull &&
+                      (ctx->bin == 1 || (ctx->bin < 0 && sp.n >= ctx->bin_min && !forced_geometry(ctx)));
+  // the plan cache serves the binned path, and below the binning threshold
+  // unforced batches of a plan's size
+  const bool planned = !hooked && ctx->bin < 0 && ctx->bin_plan < 0 && ctx->plan_host &&
+                       (binned || (!forced_geometry(ctx) && plan_sized(sp)));
+  const PlanRead pr = planned ? plan_lookup(ctx, sp) : PlanRead{};
+  const Launch L = choose_checksum(ctx, sp, d_odd != nullptr, binned, pr);
+  return issue_checksum(ctx, sp, d_init, d_odd, d_out, out_kind, L, pr.req, st);
+}
+
+int ipv4_device(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip_ck, uint16_t* d_tcp_ck,
+                uint8_t* d_status, hipStream_t st) {
+  const bool planned = plan_sized(sp) && !forced_geometry(ctx) && !ctx->twoclass;
+  const PlanRead pr = planned ? plan_lookup(ctx, sp) : PlanRead{};
+  return issue_ipv4(ctx, sp, mode, d_ip_ck, d_tcp_ck, d_status, choose_ipv4(ctx, sp, pr), pr.req, st);
+}
+
+int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msgs, uint32_t* hdr_out,
+                uint16_t* d_ip_ck, uint16_t* d_tcp_ck, bool payload_only, uint64_t hint, hipStream_t st) {
+  const PlanRead pr = plan_sized(sp) && !forced_geometry(ctx) ? plan_lookup(ctx, sp) : PlanRead{};
+  const Launch L = choose_wrap(ctx, sp, hdr_out != nullptr, payload_only, hint, pr);
+  return issue_wrap(ctx, sp, d_msgs, hdr_out, d_ip_ck, d_tcp_ck, payload_only, L, pr.req, st);
 }
 
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st) {
   if (d_hdrs) {
     ICS_HIP(icsum::launch_router_hdrs(sp, d_hdrs, d_status, st));
-    note(ctx, ICS_K_ROUTER_HDRS);
+    report_launch(ctx, ICS_K_ROUTER_HDRS);
   } else {
     ICS_HIP(icsum::launch_router_ttl(sp, d_status, st));
-    note(ctx, ICS_K_ROUTER);
+    report_launch(ctx, ICS_K_ROUTER);
   }
   return ICS_OK;
-}
-
-namespace {
-// the table stays locked (its image valid) until the image is on the device
-struct RouteImageLock {
-  ics_route_table* tbl = nullptr;
-  ~RouteImageLock() {
-    if (tbl) route_image_release(tbl);
-  }
-};
-}  // namespace
-
-namespace {
-// The slot of `slots` that holds image (id, gen), uploaded on `st` when it is
-// not there yet: the slot with that id, else the least recently used (an
-// empty one first).  The caller holds ctx->route_mu and the table's lock (the
-// host image `words` stays valid until the upload has landed).
-int image_slot(ics_ctx* ctx, ics_ctx::RouteSlot (&slots)[ics_ctx::kRouteSlots], uint64_t id, uint64_t gen,
-               const uint32_t* words, size_t need, uint64_t a, uint32_t b, hipStream_t st,
-               ics_ctx::RouteSlot** out) {
-  ics_ctx::RouteSlot* slot = nullptr;
-  for (auto& s : slots)
-    if (s.id == id) slot = &s;
-  if (!slot) {
-    slot = &slots[0];
-    for (auto& s : slots)
-      if (s.used < slot->used) slot = &s;
-  }
-  if (slot->id != id || slot->gen != gen) {
-    slot->id = 0;  // not trusted until the upload has landed
-    if (slot->launched) ICS_HIP(hipEventSynchronize(slot->ev));  // a launch on another stream may still read it
-    if (need > slot->cap) {
-      const size_t cap = (std::max(need, 2 * slot->cap) + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
-      void* p = nullptr;
-      ICS_HIP(hipMalloc(&p, cap));
-      if (slot->d) ctx->route_retired.push_back(slot->d);
-      slot->d = static_cast<uint32_t*>(p);
-      slot->cap = cap;
-    }
-    ICS_HIP(hipMemcpyAsync(slot->d, words, need, hipMemcpyHostToDevice, st));
-    ICS_HIP(hipStreamSynchronize(st));  // the table's host image is released by the caller
-    slot->id = id;
-    slot->gen = gen;
-    slot->nwords = a;
-    slot->nrecs = b;
-  }
-  slot->used = ++ctx->route_clock;
-  if (!slot->ev) ICS_HIP(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
-  *out = slot;
-  return ICS_OK;
-}
-
-int route_slot_for(ics_ctx* ctx, ics_route_table* tbl, hipStream_t st, ics_ctx::RouteSlot** out) {
-  RouteImageView v;
-  if (int rc = route_image_acquire(tbl, &v)) return rc;
-  RouteImageLock held{tbl};
-  return image_slot(ctx, ctx->route_slot, v.id, v.gen, v.words, (size_t(v.nwords) + 2 * size_t(v.nrecs)) * 4,
-                    v.nwords, v.nrecs, st, out);
-}
-
-struct NeighImageLock {
-  ics_neigh_table* tbl = nullptr;
-  ~NeighImageLock() {
-    if (tbl) neigh_image_release(tbl);
-  }
-};
-
-// a neighbour image's slot: nwords holds the identity entries, nrecs the hash slots
-int neigh_slot_for(ics_ctx* ctx, ics_neigh_table* tbl, hipStream_t st, ics_ctx::RouteSlot** out) {
-  NeighImageView v;
-  if (int rc = neigh_image_acquire(tbl, &v)) return rc;
-  NeighImageLock held{tbl};
-  return image_slot(ctx, ctx->neigh_slot, v.id, v.gen, v.words, (size_t(v.nif) + size_t(v.nslots)) * 16, v.nif,
-                    v.nslots, st, out);
-}
-
-// the launch that read the slot is behind its event, or nothing may replace the image under it
-void slot_launched(ics_ctx::RouteSlot* slot, hipStream_t st) {
-  if (hipEventRecord(slot->ev, st) == hipSuccess) {
-    slot->launched = true;
-  } else {
-    (void)hipStreamSynchronize(st);
-    slot->launched = false;
-  }
-}
-}  // namespace
-
-int route_device(ics_ctx* ctx, ics_route_table* tbl, const icsum::SegSpec* sp, const uint32_t* d_addrs, uint64_t n,
-                 uint32_t* d_hdrs, uint8_t* d_status, uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st) {
-  std::lock_guard<std::mutex> lock(ctx->route_mu);
-  ics_ctx::RouteSlot* slot = nullptr;
-  if (int rc = route_slot_for(ctx, tbl, st, &slot)) return rc;
-  const icsum::RouteImg img{slot->d, slot->nwords, slot->nrecs};
-  if (!sp) {
-    ICS_HIP(icsum::launch_route_lookup(d_addrs, n, img, d_iface, d_next_hop, st));
-    note(ctx, ICS_K_ROUTE_LOOKUP);
-  } else {
-    ICS_HIP(icsum::launch_router_route(*sp, img, d_hdrs, d_status, d_iface, d_next_hop, st));
-    note(ctx, d_hdrs ? ICS_K_ROUTER_ROUTE_HDRS : ICS_K_ROUTER_ROUTE);
-  }
-  slot_launched(slot, st);
-  return ICS_OK;
-}
-
-int frames_device(ics_ctx* ctx, ics_route_table* routes, ics_neigh_table* neigh, const icsum::SegSpec& sp,
-                  uint32_t in_iface, const uint32_t* d_in_iface, uint32_t* d_hdrs, uint8_t* d_status,
-                  uint32_t* d_iface, uint32_t* d_next_hop, hipStream_t st) {
-  std::lock_guard<std::mutex> lock(ctx->route_mu);
-  ics_ctx::RouteSlot *rs = nullptr, *ns = nullptr;
-  if (routes)
-    if (int rc = route_slot_for(ctx, routes, st, &rs)) return rc;
-  if (int rc = neigh_slot_for(ctx, neigh, st, &ns)) return rc;
-  const icsum::RouteImg rimg = rs ? icsum::RouteImg{rs->d, rs->nwords, rs->nrecs} : icsum::RouteImg{};
-  const icsum::NeighImg nimg{ns->d, uint32_t(ns->nwords), ns->nrecs};
-  ICS_HIP(icsum::launch_frames(sp, rimg, nimg, in_iface, d_in_iface, routes ? d_hdrs : nullptr, d_status, d_iface,
-                               d_next_hop, st));
-  note(ctx, routes ? ICS_K_ROUTER_FRAMES : ICS_K_FRAME_RECV);
-  if (rs) slot_launched(rs, st);
-  slot_launched(ns, st);
-  return ICS_OK;
-}
-
-void free_routes(ics_ctx* ctx) {
-  for (auto* slots : {&ctx->route_slot, &ctx->neigh_slot})
-    for (auto& s : *slots) {
-      if (s.launched) (void)hipEventSynchronize(s.ev);
-      if (s.d) (void)hipFree(s.d);
-      if (s.ev) (void)hipEventDestroy(s.ev);
-      s = {};
-    }
-  for (void* p : ctx->route_retired) (void)hipFree(p);
-  ctx->route_retired.clear();
 }
 
 namespace {
@@ -670,7 +533,7 @@ int run_batchv(ics_ctx* ctx, const D* b, uint32_t k, ClassFn cls_of, LaunchFn la
     }
     if (int rc = flush()) return rc;
   }
-  if (last_cls >= 0) note(ctx, ICS_K_BATCHV, {last_cls, int(k), true, 0, 1});
+  if (last_cls >= 0) report_launch(ctx, ICS_K_BATCHV, last_cls, int(k));
   return ICS_OK;
 }
 }  // namespace

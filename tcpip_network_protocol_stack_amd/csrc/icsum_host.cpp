@@ -449,14 +449,6 @@ int server_stop(ics_ctx* ctx) {
 // synchronisation).
 namespace {
 
-// ics_dispatch_info's "last call" fields for a host-memory call's launch
-void note_host(ics_ctx* ctx, int kernel, int lps, int unroll) {
-  ctx->last_kernel.store(kernel, std::memory_order_relaxed);
-  ctx->last_lps.store(lps, std::memory_order_relaxed);
-  ctx->last_unroll.store(unroll, std::memory_order_relaxed);
-  ctx->last_plan.store(-1, std::memory_order_relaxed);
-}
-
 int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offsets, uint64_t stride,
                  uint64_t seg_len, const uint32_t* h_init, uint64_t n, int mode, uint16_t* out_a, uint16_t* out_b,
                  uint8_t* out_c, const ics_tcp_msg* h_msgs) {
@@ -620,7 +612,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       if (int rc = server_post(ctx, kind, dev_mode, bytes_in, d_init, out, h_offsets ? ctx->h_off[slot] : nullptr,
                                stride, seg_len, uint32_t(m), &srv_of[slot]))
         return rc;
-      note_host(ctx, ICS_K_TICK_SERVER, 16, 8);
+      report_launch(ctx, ICS_K_TICK_SERVER, 16, 8);
     } else if (tick) {
       const uint32_t* d_init = nullptr;
       if (kind == 0 && h_init) {
@@ -631,19 +623,18 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       const int dev_mode = mode == ICS_MODE_PATCH ? ICS_MODE_COMPUTE : mode;  // PATCH: fields written at retire
       ICS_HIP(icsum::launch_tick(in, ctx->h_off[slot], uint32_t(m), kind == 0 ? 0 : 1, d_init, a, dev_mode, a, a + m,
                                  res + m * 4, ctx->d_zero, sp.done, st));
-      note_host(ctx, ICS_K_TICK, 16, 8);
+      report_launch(ctx, ICS_K_TICK, 16, 8);
     } else if (kind == 2) {
       std::memcpy(ctx->h_msg[slot], h_msgs + c.i0, m * sizeof(ics_tcp_msg));
       const void* msgs = nullptr;
       ICS_HIP(h2d(ctx->d_msg[slot], ctx->h_msg[slot], m * sizeof(ics_tcp_msg), &msgs));
       uint8_t* hdr = zc ? ctx->h_hdr[slot] : ctx->d_hdr[slot];
+      const icsum::Geometry gw = ipv4_geometry(g);
       ICS_HIP(icsum::launch_tcp_wrap(sp, static_cast<const icsum::TcpMsg*>(msgs), reinterpret_cast<uint32_t*>(hdr),
                                      nullptr, nullptr, mode == 1,
-                                     wrap_two_pass(ctx, true, m) ? ctx->d_sums[slot] : nullptr, ipv4_geometry(g),
-                                     0, st));
+                                     wrap_two_pass(ctx, true, m) ? ctx->d_sums[slot] : nullptr, gw, 0, st));
       ICS_HIP(d2h(ctx->h_hdr[slot], ctx->d_hdr[slot], m * 40));
-      note_host(ctx, wrap_two_pass(ctx, true, m) ? ICS_K_WRAP_2PASS : ICS_K_WRAP, ipv4_geometry(g).lps,
-                ipv4_geometry(g).unroll);
+      report_launch(ctx, wrap_two_pass(ctx, true, m) ? ICS_K_WRAP_2PASS : ICS_K_WRAP, gw.lps, gw.unroll);
     } else if (kind == 0) {
       const uint32_t* d_init = nullptr;
       if (h_init) {
@@ -654,8 +645,8 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       }
       ICS_HIP(icsum::launch_checksum(sp, d_init, nullptr, res, 0, g, 0, st));
       ICS_HIP(d2h(ctx->h_out[slot], ctx->d_out[slot], m * 2));
-      note_host(ctx, g.mode == icsum::kModeTiny ? ICS_K_TINY : g.segs > 1 ? ICS_K_SMALL : ICS_K_CHECKSUM, g.lps,
-                g.unroll);
+      report_launch(ctx, g.mode == icsum::kModeTiny ? ICS_K_TINY : g.segs > 1 ? ICS_K_SMALL : ICS_K_CHECKSUM, g.lps,
+                    g.unroll);
     } else {
       uint16_t* a = reinterpret_cast<uint16_t*>(res);
       uint16_t* b = a + m;
@@ -668,7 +659,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       const icsum::Geometry gi = h_offsets ? ipv4_geometry(g) : ipv4_fixed_geometry(ctx, ipv4_geometry(g), seg_len);
       ICS_HIP(icsum::launch_ipv4_tcp(sp, dev_mode, a, b, s, gi, 0, st));
       ICS_HIP(d2h(ctx->h_out[slot], ctx->d_out[slot], m * 5));
-      note_host(ctx, ICS_K_IPV4, gi.lps, gi.unroll);
+      report_launch(ctx, ICS_K_IPV4, gi.lps, gi.unroll);
     }
     if (!zc) ICS_HIP(hipEventRecord(ctx->ev[slot], st));
     pending[slot] = c;

@@ -1,5 +1,5 @@
 // icsum_neigh.h — internal to libicsum.so: the compiled image of a neighbour
-// table (icsum_neigh.cpp) as the device path (icsum_dispatch.cpp) takes it.
+// table (icsum_neigh.cpp) as the device path (icsum_images.cpp) takes it.
 // Plain C++, no HIP.  Not installed, not part of the ABI.
 //
 // Image: one uint32 array, 4 * nif identity words, then 4 * nslots slot words.

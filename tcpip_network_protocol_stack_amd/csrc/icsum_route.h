@@ -1,5 +1,5 @@
 // icsum_route.h — internal to libicsum.so: the compiled image of a route
-// table (icsum_route.cpp) as the device path (icsum_dispatch.cpp) takes it.
+// table (icsum_route.cpp) as the device path (icsum_images.cpp) takes it.
 // Plain C++, no HIP.  Not installed, not part of the ABI.
 //
 // Image: nwords trie words, then two words per route record.
