@@ -435,6 +435,66 @@ int ics_tcp_wrap_headers(ics_ctx* ctx, const void* d_payloads, const uint64_t* d
                          uint64_t payload_len, uint64_t n, const ics_tcp_msg* d_msgs, void* d_hdrs,
                          uint16_t* d_ip_ck, uint16_t* d_tcp_ck, void* stream);
 
+/* ---- device-side unwrap_tcp_in_ip: message records from a datagram batch - */
+/* The mirror of ics_tcp_wrap_headers: what TCPOverIPv4Adapter::unwrap_tcp_in_ip
+ * (util/tcp_over_ip/tcp_over_ip.cpp:14-64) and TCPSegment::parse
+ * (util/tcp_segment/tcp_segment.cpp:25-65) read out of a datagram's bytes, as
+ * one 40-byte record per datagram.  Let L be the datagram's length and
+ * `status` the byte ICS_MODE_VERIFY writes for it, bit for bit.  PARSED means
+ * (status & 7) == 7: ICS_ST_IPV4_OK, ICS_ST_TCP_CKSUM_OK and ICS_ST_TCP_HDR_OK.
+ *   - Not PARSED: the 36 bytes before `status` are zero.
+ *   - PARSED: hl = 4 * hlen (20..60), and TCP_HDR_OK guarantees hl + 20 <= L.
+ *     With T the byte at hl:
+ *       msg.src, msg.dst   header bytes 12-15 and 16-19, host order
+ *       msg.ttl, msg.id    header byte 8, header bytes 4-5
+ *       msg.src_port       T[0..1]        msg.dst_port  T[2..3]
+ *       msg.seqno          T[4..7]
+ *       msg.ackno          T[8..11] if T[13] & 0x10, else 0 (tcp_segment.cpp:42-45
+ *                          resets an absent ackno; :86 serializes it as 0)
+ *       msg.flags          T[13] & 0x17, the ICS_TCP_* bits
+ *       msg.window         T[14..15]      msg.reserved  0
+ *       pay_off            min(hl + 4 * doff, L), doff = T[12] >> 4 (>= 5)
+ *       pay_len            (L - pay_off) mod 2^32
+ *   - Options that claim more than the datagram holds: the payload is empty,
+ *     no error (Parser::remove_prefix stops at the end, util/tools/parser.h:54-68).
+ *   - proto != 6 does not affect PARSED and the fields are filled:
+ *     ICS_ST_PROTO_TCP in `status` is what unwrap_tcp_in_ip:26 gates on.
+ *   - The adapter's gates (tcp_over_ip.cpp:14-23, 39-64: destination and source
+ *     address, ports, the listening -> connected transition, sequential in
+ *     batch order) stay with the caller; they need only record fields.
+ *   - Round trip: for a PARSED datagram with hlen 5, tos 0, fragment field
+ *     0x4000, proto 6 (what wrap_tcp_in_ip writes, tcp_over_ip.cpp:69-88),
+ *     len == L mod 2^16, doff 5, urgent 0 and no flag bits outside 0x17,
+ *     ics_tcp_wrap_headers on rec.msg and [pay_off, pay_off + pay_len)
+ *     reproduces its first 40 wire bytes. */
+typedef struct ics_tcp_rx {   /* 40 bytes; arrays of it 4-byte aligned */
+  ics_tcp_msg msg;            /* exactly what ics_tcp_wrap_* takes (28 bytes) */
+  uint32_t pay_off;           /* TCPSenderMessage::payload starts this many bytes into the datagram */
+  uint32_t pay_len;           /* and has this many bytes */
+  uint8_t status;             /* the ICS_ST_* byte ICS_MODE_VERIFY writes for this datagram */
+  uint8_t reserved[3];        /* 0 */
+} ics_tcp_rx;
+
+/* One datagram on the host: no context, no GPU.  Computes both checksums
+ * itself (ipv4_header.cpp:9-59, tcp_segment.cpp:11-18), so *out is the whole
+ * record, status included.  dgram may be NULL only when len is 0. */
+int ics_tcp_unwrap_one(const void* dgram, size_t len, ics_tcp_rx* out);
+
+/* n datagrams on the device (addressing as ics_ipv4_tcp_batch): the VERIFY
+ * pass of ics_ipv4_tcp_batch on `stream` — its status bytes to d_status, or
+ * to context scratch when d_status is NULL — then k_tcp_unwrap on the same
+ * stream, one lane per datagram, reading only the header blocks: two launches
+ * (the tuned verify kernels are left as they are).  d_recs:
+ * n records, 4-byte aligned.  The datagrams are only read. */
+int ics_tcp_unwrap_batch(ics_ctx* ctx, const void* d_dgrams, const uint64_t* d_offsets, uint64_t stride,
+                         uint64_t dgram_len, uint64_t n, ics_tcp_rx* d_recs, uint8_t* d_status, void* stream);
+
+/* The same on host memory: the datagrams go to the device (or are read in
+ * place when the batch is small and page-locked), only the 40-byte records
+ * come back.  Synchronous. */
+int ics_tcp_unwrap_batch_host(ics_ctx* ctx, const void* h_dgrams, const uint64_t* h_offsets, uint64_t stride,
+                              uint64_t dgram_len, uint64_t n, ics_tcp_rx* h_recs);
+
 /* ---- several batches in one launch -------------------------------------- */
 /* The receive and transmit paths hand the engine a stream of small batches —
  * one per event-loop tick or per filled arena (the reference reads its TUN fd
@@ -546,6 +606,7 @@ int ics_stream_synchronize(ics_ctx* ctx, void* stream);
 #define ICS_K_ROUTER_ROUTE_HDRS 19 /* k_router_hdrs with the route lookup fused */
 #define ICS_K_FRAME_RECV 20      /* k_frame<false>: recv_frame's classification (0 / 0) */
 #define ICS_K_ROUTER_FRAMES 21   /* k_frame<true>: the whole hop over Ethernet frames (0 / 0) */
+#define ICS_K_UNWRAP 22          /* k_tcp_unwrap behind the VERIFY launch: ics_tcp_unwrap_batch(_host) (0 / 0) */
 /* last_lps / last_unroll by kernel:
  *   ICS_K_CHECKSUM .. ICS_K_WRAP_2PASS  lanes per segment / loads in flight per lane
  *   ICS_K_TWOCLASS, ICS_K_IPV4_TWOCLASS  long-segment lanes (16) / segments per wave (16 or 32; 8 only under ICSUM_FORCE twoclass=8)

@@ -33,6 +33,16 @@ class TcpMsg(ctypes.Structure):
 assert ctypes.sizeof(TcpMsg) == 28
 
 
+class TcpRx(ctypes.Structure):
+    """struct ics_tcp_rx (include/icsum.h), 40 bytes: what unwrap_tcp_in_ip and
+    TCPSegment::parse read out of one datagram (ics_tcp_unwrap_*)."""
+    _fields_ = [("msg", TcpMsg), ("pay_off", ctypes.c_uint32), ("pay_len", ctypes.c_uint32),
+                ("status", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+assert ctypes.sizeof(TcpRx) == 40
+
+
 class DispatchInfo(ctypes.Structure):
     """struct ics_dispatch_info_t (include/icsum.h): the last call's launch and
     the plan cache's counters."""
@@ -73,7 +83,7 @@ class NeighStats(ctypes.Structure):
 KERNELS = {1: "checksum", 2: "small", 3: "tiny", 4: "dense", 5: "twoclass", 6: "binned", 7: "ipv4",
            8: "ipv4_twoclass", 9: "wrap", 10: "wrap_2pass", 11: "router", 12: "batchv", 13: "tile",
            14: "router_hdrs", 15: "tick", 16: "tick_server", 17: "route_lookup", 18: "router_route",
-           19: "router_route_hdrs", 20: "frame_recv", 21: "router_frames"}
+           19: "router_route_hdrs", 20: "frame_recv", 21: "router_frames", 22: "unwrap"}
 ICS_RT_FORWARD, ICS_RT_ROUTED = 0x01, 0x02
 ICS_NO_ROUTE = 0xFFFFFFFF
 ICS_FR_RESOLVED, ICS_FR_DGRAM, ICS_FR_FOR_US, ICS_FR_IPV4, ICS_FR_ARP, ICS_FR_ARP_OK = 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
@@ -130,7 +140,10 @@ SIGNATURES = {
     "ics_tcp_wrap_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p]),
     "ics_tcp_wrap_headers": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p, _p, _p]),
     "ics_tcp_wrap_headers_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p]),
-    "ics_checksum_batch_host": (_int, [_p, _p, _p, _u64, _u64, _p, _p, _u64]),
+    "ics_tcp_unwrap_one": (_int, [_p, ctypes.c_size_t, ctypes.POINTER(TcpRx)]),
+    "ics_tcp_unwrap_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p]),
+    "ics_tcp_unwrap_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p]),
+    "ics_checksum_batch_host": (_int,[_p, _p, _p, _u64, _u64, _p, _p, _u64]),
     "ics_ipv4_tcp_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _int, _p, _p, _p]),
     "ics_malloc": (_int, [_p, ctypes.POINTER(_p), ctypes.c_size_t]),
     "ics_free": (_int, [_p, _p]),

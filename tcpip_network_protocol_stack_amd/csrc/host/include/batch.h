@@ -10,6 +10,7 @@
 //                         (headers + both checksums serialized on the GPU;
 //                         payloads copied once, into the DMA arena)
 //   unwrap()/unwrap_raw() TCPOverIPv4Adapter::unwrap_tcp_in_ip per datagram tcp_over_ip.cpp:10-67
+//   unwrap_records()      the same from the device's ics_tcp_rx records (fields parsed on the GPU)
 //
 // Results are bit-identical to the per-object calls.  All checksum arithmetic
 // runs on the GPU; a BatchEngine cannot be constructed without one (there is
@@ -73,6 +74,12 @@ class BatchEngine
     void wrap_packed(uint8_t* bytes, const uint64_t* offsets, const ics_tcp_msg* msgs, size_t n);
     std::vector<std::optional<TCPMessage>> unwrap_packed(TCPOverIPv4Adapter& adapter, const uint8_t* bytes,
                                                          const uint64_t* offsets, size_t n);
+    // the same results from the device's message records
+    // (ics_tcp_unwrap_batch_host: one 40-byte ics_tcp_rx per datagram, no host
+    // pass over the headers): the adapter's gates applied from record fields
+    // in datagram order, one payload copy per accepted datagram
+    std::vector<std::optional<TCPMessage>> unwrap_records(TCPOverIPv4Adapter& adapter, const uint8_t* bytes,
+                                                          const uint64_t* offsets, size_t n);
 
     // the resident tick server (ics_set_tick_server): a per-tick loop's calls
     // of <= 16 x blocks datagrams without a kernel launch each; 0 turns it

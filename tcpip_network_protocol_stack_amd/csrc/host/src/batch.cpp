@@ -380,4 +380,40 @@ std::vector<std::optional<TCPMessage>> BatchEngine::unwrap_packed(TCPOverIPv4Ada
     return out;
 }
 
+std::vector<std::optional<TCPMessage>> BatchEngine::unwrap_records(TCPOverIPv4Adapter& adapter, const uint8_t* bytes,
+                                                                   const uint64_t* offsets, size_t n)
+{
+    // receive path with the field parse on the device too: the records carry
+    // everything the gates read, so the host touches a datagram's bytes only
+    // to copy the payload of one it accepts
+    std::vector<std::optional<TCPMessage>> out(n);
+    if (n == 0) return out;
+    std::vector<ics_tcp_rx> rec(n);
+    check(ics_tcp_unwrap_batch_host(ctx_, bytes, offsets, 0, 0, n, rec.data()), "ics_tcp_unwrap_batch_host");
+    constexpr uint8_t kParsed = ICS_ST_IPV4_OK | ICS_ST_TCP_CKSUM_OK | ICS_ST_TCP_HDR_OK;
+    for (size_t i = 0; i < n; ++i) {
+        const ics_tcp_rx& r = rec[i];
+        if ((r.status & kParsed) != kParsed) continue;
+        IPv4Header h;  // the three fields the gates read
+        h.src = r.msg.src;
+        h.dst = r.msg.dst;
+        h.proto = (r.status & ICS_ST_PROTO_TCP) ? IPv4Header::PROTO_TCP : uint8_t{0};  // any other value fails ip_gate
+        if (!detail::ip_gate(adapter, h)) continue;
+        TCPSegment seg;
+        seg.udinfo.src_port = r.msg.src_port;
+        seg.udinfo.dst_port = r.msg.dst_port;
+        TCPMessage& m = seg.message;
+        m.sender.seqno = Wrap32{r.msg.seqno};
+        m.sender.SYN = (r.msg.flags & ICS_TCP_SYN) != 0;
+        m.sender.FIN = (r.msg.flags & ICS_TCP_FIN) != 0;
+        m.sender.RST = m.receiver.RST = (r.msg.flags & ICS_TCP_RST) != 0;
+        if (r.msg.flags & ICS_TCP_ACK) m.receiver.ackno = Wrap32{r.msg.ackno};
+        m.receiver.window_size = r.msg.window;
+        out[i] = detail::tcp_gate(adapter, h, std::move(seg));
+        if (out[i] && r.pay_len)
+            out[i]->sender.payload.assign(reinterpret_cast<const char*>(bytes) + offsets[i] + r.pay_off, r.pay_len);
+    }
+    return out;
+}
+
 }  // namespace icsum

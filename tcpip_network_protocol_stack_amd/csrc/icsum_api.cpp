@@ -144,6 +144,7 @@ int ics_destroy(ics_ctx* ctx) {
     if (ctx->d_zero) (void)hipFree(ctx->d_zero);
     if (ctx->plan_host) (void)hipHostFree(ctx->plan_host);
     ctx->scratch.release();
+    ctx->unwrap_status.release();
   }
   delete ctx;
   return ICS_OK;
@@ -263,6 +264,29 @@ int ics_tcp_wrap_headers(ics_ctx* ctx, const void* d_payloads, const uint64_t* d
   hipStream_t st = static_cast<hipStream_t>(stream);
   return bounds_verdict(st, wrap_device(ctx, sp, d_msgs, static_cast<uint32_t*>(d_hdrs), d_ip_ck, d_tcp_ck, true,
                                         1000, st));
+}
+
+int ics_tcp_unwrap_batch(ics_ctx* ctx, const void* d_dgrams, const uint64_t* d_offsets, uint64_t stride,
+                         uint64_t dgram_len, uint64_t n, ics_tcp_rx* d_recs, uint8_t* d_status, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (n == 0) return ICS_OK;
+  if (!d_dgrams) return fail(ICS_ERR_INVALID, "null datagram buffer");
+  if (!d_recs) return fail(ICS_ERR_INVALID, "null record array");
+  if (reinterpret_cast<uintptr_t>(d_recs) & 3u) return fail(ICS_ERR_INVALID, "record array not 4-byte aligned");
+  const icsum::SegSpec sp{static_cast<const uint8_t*>(d_dgrams), d_offsets, stride, dgram_len, n, ctx->d_zero};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, unwrap_device(ctx, sp, d_recs, d_status, st));
+}
+
+int ics_tcp_unwrap_batch_host(ics_ctx* ctx, const void* h_dgrams, const uint64_t* h_offsets, uint64_t stride,
+                              uint64_t dgram_len, uint64_t n, ics_tcp_rx* h_recs) {
+  if (int rc = bind(ctx)) return rc;
+  if (n == 0) return ICS_OK;
+  if (!h_dgrams) return fail(ICS_ERR_INVALID, "null host buffer");
+  if (!h_recs) return fail(ICS_ERR_INVALID, "null record array");
+  if (reinterpret_cast<uintptr_t>(h_recs) & 3u) return fail(ICS_ERR_INVALID, "record array not 4-byte aligned");
+  return host_pipeline(ctx, 3, const_cast<void*>(h_dgrams), h_offsets, stride, dgram_len, nullptr, n, 0, nullptr,
+                       nullptr, reinterpret_cast<uint8_t*>(h_recs), nullptr);
 }
 
 int ics_checksum_batchv(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, void* stream) {

@@ -163,6 +163,11 @@ struct ics_ctx {
   // device scratch of the binned dispatch and the two-pass wrap (a binned
   // batch of n segments: 80 n bytes + 16 KiB; a two-pass wrap: 4 n)
   icsum::detail::ScratchArea scratch;
+  // ics_tcp_unwrap_batch without d_status: the VERIFY launch's n status bytes.
+  // An area of its own, because the VERIFY dispatch behind it may lease
+  // `scratch` for its re-plan while this lease is held; its event is created
+  // on first use (unwrap_device).
+  icsum::detail::ScratchArea unwrap_status;
   std::mutex mu;
   // host path: nslots slots (2..kMaxSlots, ICSUM_HOST_SLOTS) of slot_bytes each
   // (ICSUM_HOST_SLOT_MB), each with pinned in/out staging, device buffers and a stream
@@ -351,6 +356,9 @@ int ipv4_device(ics_ctx* ctx, const icsum::SegSpec& sp, int mode, uint16_t* d_ip
 // hint = the mean length an offsets batch is assumed to have before its plan lands.
 int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msgs, uint32_t* hdr_out,
                 uint16_t* d_ip_ck, uint16_t* d_tcp_ck, bool payload_only, uint64_t hint, hipStream_t st);
+// unwrap_tcp_in_ip's parse: ipv4_device in VERIFY mode (status to d_status, or
+// to ctx->unwrap_status when null), then k_tcp_unwrap's records to d_recs.
+int unwrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, ics_tcp_rx* d_recs, uint8_t* d_status, hipStream_t st);
 // c2: the router's TTL decrement + header checksum recompute, in place
 // (d_hdrs null) or with the forwarded headers to d_hdrs (20 bytes each).
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st);
@@ -376,7 +384,9 @@ void free_routes(ics_ctx* ctx);
 // ---- icsum_host.cpp: the host-memory pipeline.
 // kind 0: checksum batch (u16 out); kind 1: ipv4_tcp batch (ip u16, tcp u16, status u8);
 // kind 2: tcp wrap (40 header bytes per datagram back, written into h_bytes, or
-// into out_c for mode 1 = payload-only).  Returns with every result in place.
+// into out_c for mode 1 = payload-only); kind 3: tcp unwrap (one 40-byte
+// ics_tcp_rx per datagram back into out_c; the bytes are only read).  Returns
+// with every result in place.
 int host_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offsets, uint64_t stride,
                   uint64_t seg_len, const uint32_t* h_init, uint64_t n, int mode, uint16_t* out_a, uint16_t* out_b,
                   uint8_t* out_c, const ics_tcp_msg* h_msgs = nullptr);

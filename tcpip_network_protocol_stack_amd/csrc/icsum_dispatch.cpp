@@ -485,6 +485,25 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
   return issue_wrap(ctx, sp, d_msgs, hdr_out, d_ip_ck, d_tcp_ck, payload_only, L, pr.req, st);
 }
 
+// The VERIFY dispatch exactly as ics_ipv4_tcp_batch runs it (same plan cache
+// slot, same choice), then one more launch on the stream for the records.
+int unwrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, ics_tcp_rx* d_recs, uint8_t* d_status, hipStream_t st) {
+  std::unique_ptr<Scratch> lease;  // without d_status: held until both launches are enqueued
+  if (!d_status) {
+    {
+      std::lock_guard<std::mutex> lock(ctx->unwrap_status.mu);
+      if (!ctx->unwrap_status.ev) ICS_HIP(hipEventCreateWithFlags(&ctx->unwrap_status.ev, hipEventDisableTiming));
+    }
+    lease = std::make_unique<Scratch>(ctx->unwrap_status, sp.n, st);
+    ICS_HIP(lease->error());
+    d_status = static_cast<uint8_t*>(lease->get());
+  }
+  if (int rc = ipv4_device(ctx, sp, ICS_MODE_VERIFY, nullptr, nullptr, d_status, st)) return rc;
+  ICS_HIP(icsum::launch_tcp_unwrap(sp, d_status, reinterpret_cast<uint32_t*>(d_recs), st));
+  report_launch(ctx, ICS_K_UNWRAP);
+  return ICS_OK;
+}
+
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st) {
   if (d_hdrs) {
     ICS_HIP(icsum::launch_router_hdrs(sp, d_hdrs, d_status, st));

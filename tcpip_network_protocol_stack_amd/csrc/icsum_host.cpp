@@ -439,7 +439,9 @@ int server_stop(ics_ctx* ctx) {
 }
 
 // kind 0: checksum batch (u16 out); kind 1: ipv4_tcp batch (ip u16, tcp u16, status u8);
-// kind 2: tcp wrap (40 header bytes per datagram back, written into h_bytes).
+// kind 2: tcp wrap (40 header bytes per datagram back, written into h_bytes);
+// kind 3: tcp unwrap (one 40-byte record per datagram back; the staged path and
+// the single zero-copy launch pair only, never k_tick or the tick server).
 // The slots take turns, one stream each: while the GPU moves and sums chunk
 // k, the host prepares chunk k+1.  Pinned user buffers are DMA'd directly (no
 // host copy); pageable ones are staged through the pinned slots by par_memcpy.
@@ -453,7 +455,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
                  uint64_t seg_len, const uint32_t* h_init, uint64_t n, int mode, uint16_t* out_a, uint16_t* out_b,
                  uint8_t* out_c, const ics_tcp_msg* h_msgs) {
   if (int rc = ensure_staging(ctx)) return rc;
-  if (kind == 2)
+  if (kind >= 2)  // the wraps' and the unwrap's 40 bytes per datagram
     if (int rc = ensure_wrap_staging(ctx)) return rc;
   const Pinned pin = host_pinned(h_bytes);
   const bool direct = pin.dma;
@@ -488,7 +490,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       }
     } else if (kind == 0) {
       std::memcpy(out_a + c.i0, ctx->h_out[k], m * 2);
-    } else if (kind == 2 && mode == 1) {  // payload-only: headers to the caller's array
+    } else if (kind == 3 || (kind == 2 && mode == 1)) {  // records / payload-only headers: to the caller's array
       std::memcpy(reinterpret_cast<uint8_t*>(out_c) + 40 * c.i0, ctx->h_hdr[k], m * 40);
     } else if (kind == 2) {  // 40 header bytes into each datagram of the caller's batch
       uint8_t* bytes = static_cast<uint8_t*>(h_bytes);
@@ -517,7 +519,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
   while (i0 < n) {
     Chunk c;
     if (int rc = next_chunk(ctx, h_offsets, stride, seg_len, n, i0, pos, kind == 0,
-                            kind == 2 ? ics_ctx::kWrapSlotSegs : ics_ctx::kSlotSegs, &c))
+                            kind >= 2 ? ics_ctx::kWrapSlotSegs : ics_ctx::kSlotSegs, &c))
       return rc;
     if (int rc = retire(slot)) return rc;
     const uint64_t m = c.i1 - c.i0, nb = c.b1 - c.b0;
@@ -576,15 +578,17 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
     icsum::SegSpec sp{in, d_off, stride, seg_len, m, ctx->d_zero};
     // zero-copy: the launch itself stores the completion word (one launch per
     // call, DESIGN.md §6 "Per-tick host batches"); staged: an event
-    flag_of[slot] = zc ? ++ctx->flag_ticket : 0;
-    if (zc) sp.done = icsum::Done{ctx->d_ticket + 16 * slot, ctx->h_flag + 8 * slot, flag_of[slot]};
+    // (the unwrap's two launches: an event, like a staged chunk)
+    const bool by_flag = zc && kind != 3;
+    flag_of[slot] = by_flag ? ++ctx->flag_ticket : 0;
+    if (by_flag) sp.done = icsum::Done{ctx->d_ticket + 16 * slot, ctx->h_flag + 8 * slot, flag_of[slot]};
     const uint64_t avg = h_offsets ? nb / m : seg_len;
     const icsum::Geometry g = geometry_for(ctx, avg);
     // a zero-copy tick of a few segments with offsets: the offsets travel in
     // the kernel arguments (k_tick), not as a dependent PCIe read
-    const bool tick = zc && h_offsets && kind != 2 && m <= icsum::kTickSegs && ctx->tick_inline;
+    const bool tick = zc && h_offsets && kind < 2 && m <= icsum::kTickSegs && ctx->tick_inline;
     const bool srv =
-        zc && m <= icsum::kTickSegs * ctx->srv_blocks && ctx->srv_idle_us && (h_offsets || nb < (1u << 31));
+        kind != 3 && zc && m <= icsum::kTickSegs * ctx->srv_blocks && ctx->srv_idle_us && (h_offsets || nb < (1u << 31));
     if (srv) {  // the resident tick server takes it: no launch
       if (int rc = server_ensure(ctx)) return rc;
       const uint32_t* d_init = nullptr;  // checksum: the inits; wrap: the message records
@@ -635,6 +639,17 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
                                      wrap_two_pass(ctx, true, m) ? ctx->d_sums[slot] : nullptr, gw, 0, st));
       ICS_HIP(d2h(ctx->h_hdr[slot], ctx->d_hdr[slot], m * 40));
       report_launch(ctx, wrap_two_pass(ctx, true, m) ? ICS_K_WRAP_2PASS : ICS_K_WRAP, gw.lps, gw.unroll);
+    } else if (kind == 3) {
+      // the VERIFY launch of kind 1 with its status bytes kept in device
+      // memory, then the records: into the pinned record area (zero-copy) or
+      // copied back, 40 bytes per datagram either way
+      uint8_t* s = ctx->d_out[slot];
+      uint8_t* rec = zc ? ctx->h_hdr[slot] : ctx->d_hdr[slot];
+      const icsum::Geometry gi = h_offsets ? ipv4_geometry(g) : ipv4_fixed_geometry(ctx, ipv4_geometry(g), seg_len);
+      ICS_HIP(icsum::launch_ipv4_tcp(sp, ICS_MODE_VERIFY, nullptr, nullptr, s, gi, 0, st));
+      ICS_HIP(icsum::launch_tcp_unwrap(sp, s, reinterpret_cast<uint32_t*>(rec), st));
+      ICS_HIP(d2h(ctx->h_hdr[slot], ctx->d_hdr[slot], m * 40));
+      report_launch(ctx, ICS_K_UNWRAP);
     } else if (kind == 0) {
       const uint32_t* d_init = nullptr;
       if (h_init) {
@@ -661,7 +676,7 @@ int run_pipeline(ics_ctx* ctx, int kind, void* h_bytes, const uint64_t* h_offset
       ICS_HIP(d2h(ctx->h_out[slot], ctx->d_out[slot], m * 5));
       report_launch(ctx, ICS_K_IPV4, gi.lps, gi.unroll);
     }
-    if (!zc) ICS_HIP(hipEventRecord(ctx->ev[slot], st));
+    if (!by_flag) ICS_HIP(hipEventRecord(ctx->ev[slot], st));
     pending[slot] = c;
     busy[slot] = true;
     i0 = c.i1;

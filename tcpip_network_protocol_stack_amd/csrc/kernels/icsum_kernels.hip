@@ -27,6 +27,7 @@
 //   icsum_route.h       the route image walk (Router::match), k_route_lookup
 //   icsum_router.h      k_router_ttl, k_router_hdrs (<true>: the route lookup fused)
 //   icsum_frame.h       k_frame (<false>: recv_frame's classification, <true>: the hop over Ethernet frames)
+//   icsum_unwrap.h      k_tcp_unwrap (message records behind the VERIFY launch)
 //   icsum_span.h        k_span (tile launches)
 //   icsum_generators.h  the workload generators
 // (icsum_device.h: arithmetic primitives; icsum_launch.h: the launchers' interface)
@@ -40,6 +41,7 @@
 #include "icsum_route.h"
 #include "icsum_router.h"
 #include "icsum_frame.h"
+#include "icsum_unwrap.h"
 #include "icsum_span.h"
 #include "icsum_generators.h"
 

@@ -212,6 +212,12 @@ hipError_t launch_frames(const SegSpec& sp, const RouteImg& rt, const NeighImg& 
                          const uint32_t* in_ifaces, uint32_t* hdr_out, uint8_t* status, uint32_t* iface,
                          uint32_t* next_hop, hipStream_t st);
 
+// Message records from a datagram batch (kernels/icsum_unwrap.h): one 40-byte
+// ics_tcp_rx per datagram to recs (4-byte aligned) from the datagrams' header
+// blocks and the status bytes a VERIFY launch on the same stream left in
+// `status`.
+hipError_t launch_tcp_unwrap(const SegSpec& sp, const uint8_t* status, uint32_t* recs, hipStream_t st);
+
 // Tile launches of offsets batches (k_span): one wave per S (1..63)
 // consecutive segments, the span's bytes streamed whole in 4 KiB windows
 // whatever the lengths.  Checksum (out_kind as launch_checksum), the fused IPv4/TCP kernel

@@ -25,6 +25,10 @@ TCP_MSG_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("seqno", "<u4"), ("ac
                           ("src_port", "<u2"), ("dst_port", "<u2"), ("window", "<u2"), ("flags", "u1"),
                           ("ttl", "u1"), ("id", "<u2"), ("reserved", "<u2")])
 assert TCP_MSG_DTYPE.itemsize == 28
+# struct ics_tcp_rx (include/icsum.h) as a numpy record
+TCP_RX_DTYPE = np.dtype([("msg", TCP_MSG_DTYPE), ("pay_off", "<u4"), ("pay_len", "<u4"), ("status", "u1"),
+                         ("reserved", "u1", (3,))])
+assert TCP_RX_DTYPE.itemsize == 40
 
 
 def _ptr(t):
@@ -336,6 +340,28 @@ class Engine:
                                                msgs.ctypes.data))
         return dgrams
 
+    # ---- device-side unwrap (unwrap_tcp_in_ip, tcp_over_ip.cpp:14-64) -------
+    def tcp_unwrap_batch(self, dgrams, n=None, offsets=None, stride=0, dgram_len=0, recs=None, status=None,
+                         stream=None):
+        """One 40-byte ics_tcp_rx per datagram (include/icsum.h has the rules):
+        the VERIFY launch, then k_tcp_unwrap on the same stream.  `recs`: a
+        uint8 device tensor of 40 n bytes, 4-byte aligned (allocated when
+        absent); `status` (optional, n uint8) also receives the VERIFY status
+        bytes.  Returns recs; view it with TCP_RX_DTYPE on the host."""
+        n = _count(n, offsets, dgrams, stride)
+        recs = torch.empty(n * 40, dtype=torch.uint8, device=self.device) if recs is None else recs
+        self._check(self.lib.ics_tcp_unwrap_batch(self.ctx, _ptr(dgrams), _ptr(offsets), stride, dgram_len, n,
+                                                  _ptr(recs), _ptr(status), _stream(stream, self.device)))
+        return recs
+
+    def tcp_unwrap_batch_host(self, dgrams, n, offsets=None, stride=0, dgram_len=0, recs=None):
+        """The same on host memory (numpy uint8 datagrams); returns a
+        TCP_RX_DTYPE array of n records (`recs` when given)."""
+        recs = np.empty(n, dtype=TCP_RX_DTYPE) if recs is None else recs
+        self._check(self.lib.ics_tcp_unwrap_batch_host(self.ctx, _ptr(dgrams), _ptr(offsets), stride, dgram_len, n,
+                                                       _ptr(recs)))
+        return recs
+
     def router_ttl_batch(self, dgrams, n=None, offsets=None, stride=0, dgram_len=0, status=None,
                          stream=None):
         n = _count(n, offsets, dgrams, stride)
@@ -476,6 +502,17 @@ def device_count():
     c = ctypes.c_int()
     check(_lib.load().ics_device_count(ctypes.byref(c)))
     return c.value
+
+
+def tcp_unwrap_one(dgram, lib=None):
+    """ics_tcp_unwrap_one: the record of one datagram (bytes), computed on the
+    host with no context and no GPU; a _lib.TcpRx.  `lib`: a loaded library
+    (default libicsum.so)."""
+    lib = lib or _lib.load()
+    dgram = bytes(dgram)
+    rec = _lib.TcpRx()
+    check(lib.ics_tcp_unwrap_one(dgram, len(dgram), ctypes.byref(rec)), lib)
+    return rec
 
 
 def mixed_offsets(n, seed):

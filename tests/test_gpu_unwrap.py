@@ -1,0 +1,391 @@
+"""GPU: ics_tcp_unwrap_batch / ics_tcp_unwrap_batch_host (k_tcp_unwrap behind
+the VERIFY launch) against the Python restatement of the record
+(unwrap_ref.py, itself checked against the real reference's parses in
+test_unwrap_records.py), byte for byte over all 40 bytes, under libicsum.so and
+the bounds-checked libicsum_debug.so.
+
+Batches: every fixture datagram; n = 1, 63, 64, 65 and 2051 of mixed lengths,
+header lengths and data offsets from bases +0..+3 with the last datagram ending
+at the allocation's last byte; fixed strides; a 3000-datagram burst with every
+status class; unwrap -> ics_tcp_wrap_headers on the reference's own frames; the
+call-level cases; the host variant across chunk cuts, a slot turn and the count
+cut, equal to the device call.  All comparisons are exact."""
+import ctypes
+import os
+import random
+
+import numpy as np
+import pytest
+
+from conftest import engine_with, golden
+import host_chunks as hc
+from helpers import endtoend_capture
+from test_gpu_parity import _t
+from unwrap_ref import PARSED, canonical, load_golden, make_dgram, unwrap, verify_status
+
+pytestmark = pytest.mark.gpu
+
+LENGTHS = [0, 19, 20, 39, 40, 41, 59, 60, 61, 64, 1500]
+HLENS, DOFFS = [5, 6, 15], [4, 5, 6, 15]
+SENT = 0xA5
+
+
+@pytest.fixture(scope="module", params=[False, True], ids=["release", "debug"])
+def ueng(request):
+    gen = engine_with(None, debug=request.param)
+    yield next(gen)
+    next(gen, None)
+
+
+def pack(dgrams, lead=0):
+    off = np.zeros(len(dgrams) + 1, np.uint64)
+    off[1:] = np.cumsum([len(d) for d in dgrams])
+    return np.frombuffer(b"\xa5" * lead + b"".join(dgrams) + b"\0", np.uint8)[:lead + int(off[-1])].copy(), off + np.uint64(lead)
+
+
+def expected(dgrams):
+    return np.frombuffer(b"".join(unwrap(d) for d in dgrams), np.uint8).reshape(len(dgrams), 40)
+
+
+def verify(eng, d, n, **kw):
+    _, _, st = eng.ipv4_tcp_batch(d, 1, n=n, **kw)
+    return st.cpu().numpy()
+
+
+def run(eng, d, n, with_status=True, tail=64, **kw):
+    """the device call on batch `d`: (records n x 40, status or None); checks
+    the dispatch id and the sentinel behind 40 n"""
+    import torch
+
+    recs = torch.full((40 * n + tail,), SENT, dtype=torch.uint8, device="cuda:0")
+    st = torch.full((n + 8,), 0x5A, dtype=torch.uint8, device="cuda:0") if with_status else None
+    eng.tcp_unwrap_batch(d, n=n, recs=recs, status=st, **kw)
+    assert eng.dispatch_info()["kernel"] == "unwrap"
+    r = recs.cpu().numpy()
+    assert (r[40 * n:] == SENT).all()  # nothing written behind the last record
+    if st is not None:
+        st = st.cpu().numpy()
+        assert (st[n:] == 0x5A).all()
+        st = st[:n]
+    return r[:40 * n].reshape(n, 40), st
+
+
+def check(eng, dgrams, d, tag, **kw):
+    n = len(dgrams)
+    want = expected(dgrams)
+    got, st = run(eng, d, n, **kw)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (tag, bad[:8].tolist(), got[bad[:2]].tolist(), want[bad[:2]].tolist())
+    assert (st == got[:, 36]).all(), tag
+    assert (verify(eng, d, n, **kw) == got[:, 36]).all(), tag  # the status ICS_MODE_VERIFY returns on the same bytes
+    got2, _ = run(eng, d, n, with_status=False, **kw)  # status to context scratch
+    assert (got2 == want).all(), tag
+    return want
+
+
+def mixed(seed, n, last=None):
+    rng = random.Random(seed)
+    out = [make_dgram(rng, rng.choice(LENGTHS), rng.choice(HLENS), rng.choice(DOFFS)) for _ in range(n)]
+    if last is not None:
+        out[-1] = make_dgram(rng, last, rng.choice(HLENS), rng.choice(DOFFS), fix=1.0, flip=0.0)
+    return out
+
+
+def test_fixture_batch(ueng):
+    gold = load_golden()
+    dgrams = [bytes.fromhex(c["wire"]) for c in gold["cases"]]
+    dgrams += [bytes.fromhex(g["wire"]) for s in gold["scenarios"] for g in s["dgrams"]]
+    buf, off = pack(dgrams)
+    want = check(ueng, dgrams, _t(buf), "fixture", offsets=_t(off))
+    # ... and the fixture's own verdicts, straight from the reference
+    for i, c in enumerate(gold["cases"]):
+        parsed = want[i, 36] & PARSED == PARSED
+        assert parsed == (c["ip_parse_ok"] and c["tcp_parse_ok"]), c["tag"]
+        if parsed:
+            po, pl = int(want[i, 28:32].view("<u4")[0]), int(want[i, 32:36].view("<u4")[0])
+            assert dgrams[i][po:po + pl].hex() == c["payload"], c["tag"]
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 2051])
+def test_batch_sizes_and_bases(ueng, n):
+    """a wave's partial last group of records, more than one block; bases +0..+3, the last datagram of every
+    length in the mix ending at the allocation's last byte"""
+    import torch
+
+    for base in range(4):
+        for last in (LENGTHS[1:] if n <= 65 else [LENGTHS[(base * 3 + 1) % len(LENGTHS)] or 19, 1500]):
+            dgrams = mixed(n * 64 + base * 16 + last, n, last)
+            buf, off = pack(dgrams)
+            whole = torch.full((base + buf.size,), SENT, dtype=torch.uint8, device="cuda:0")
+            whole[base:] = torch.from_numpy(buf).cuda()
+            d = whole[base:]
+            assert d.data_ptr() % 4 == base
+            check(ueng, dgrams, d, (n, base, last), offsets=_t(off))
+            w = whole.cpu().numpy()
+            assert (w[:base] == SENT).all() and (w[base:] == buf).all()  # the datagrams are only read
+
+
+@pytest.mark.parametrize("stride,dlen", [(40, 40), (41, 41), (44, 44), (1500, 1500), (64, 40)])
+def test_fixed_strides(ueng, stride, dlen):
+    import torch
+
+    n = 300 if stride > 1000 else 2051
+    rng = random.Random(0x57 + stride)
+    dgrams = [make_dgram(rng, dlen, rng.choice(HLENS), rng.choice(DOFFS)) for _ in range(n)]
+    gap = bytes([SENT]) * (stride - dlen)
+    buf = np.frombuffer((gap.join(dgrams)), np.uint8)  # the last datagram ends the allocation
+    want = check(ueng, dgrams, _t(buf), stride, stride=stride, dgram_len=dlen)
+    parsed = (want[:, 36] & PARSED) == PARSED
+    assert parsed.any() and not parsed.all()
+    # the same from an odd base
+    whole = torch.full((3 + buf.size,), SENT, dtype=torch.uint8, device="cuda:0")
+    whole[3:] = torch.from_numpy(buf.copy()).cuda()
+    check(ueng, dgrams, whole[3:], (stride, "base 3"), stride=stride, dgram_len=dlen)
+
+
+def test_random_burst_every_status_class(ueng):
+    rng = random.Random(0xB0057)
+    dgrams = []
+    for _ in range(3000):
+        n = rng.choice(LENGTHS) if rng.random() < 0.5 else rng.randrange(0, 201)
+        dgrams.append(make_dgram(rng, n, rng.choice(HLENS + [4]), rng.choice(DOFFS)))
+    buf, off = pack(dgrams, lead=5)
+    want = check(ueng, dgrams, _t(buf), "burst", offsets=_t(off))
+    st = want[:, 36]
+    hlen = np.array([d[0] & 15 if d else 0 for d in dgrams])
+    assert (st == 0).any() and (st == 0x0F).any() and (st == 0x07).any()
+    assert ((st & 1 == 0) & (st != 0)).any()                      # the header does not parse
+    assert ((st & 3 == 3) & (st & 4 == 0)).any()                  # checksums fine, no TCP header (short, or doff 4)
+    assert ((st & 5 == 5) & (st & 2 == 0)).any()                  # a bad TCP checksum
+    assert ((st & 7 == 7) & (hlen > 5)).any() and ((st & 7 == 7) & (hlen == 5)).any()  # both load paths
+    assert (want[(st & 7) != 7][:, :36] == 0).all()
+
+
+def _reference_frames():
+    """the reference's own wrap_tcp_in_ip output: tcp_wrap.json's `wrap` cases
+    and the frames its endtoend app exchanged"""
+    out = [bytes.fromhex(c["wire"]) for c in golden("tcp_wrap.json")["cases"] if c["tag"] == "wrap"]
+    buf, _, _, starts, ends = endtoend_capture()
+    return out + [bytes(buf[int(s):int(e)]) for s, e in zip(starts, ends)]
+
+
+def test_round_trip_on_the_device(ueng):
+    """unwrap, then ics_tcp_wrap_headers on rec.msg and the payload range:
+    the first 40 wire bytes again"""
+    frames = _reference_frames()
+    ok = [d for d in frames if canonical(d)]
+    # counted on the CPU: 160 wrap cases + 269 captured datagrams, every one canonical
+    assert len(frames) == 429 and len(ok) == 429 and 10 * len(ok) >= 9 * len(frames)
+    buf, off = pack(ok, lead=2)
+    recs, _ = run(ueng, _t(buf), len(ok), offsets=_t(off))
+    assert (recs[:, 36] == 0x0F).all()
+    po, pl = recs[:, 28:32].copy().view("<u4")[:, 0], recs[:, 32:36].copy().view("<u4")[:, 0]
+    assert (po == 40).all() and (po + pl == [len(d) for d in ok]).all()
+    payloads = [d[int(a):int(a) + int(b)] for d, a, b in zip(ok, po, pl)]
+    pbuf, poff = pack(payloads)
+    msgs = np.ascontiguousarray(recs[:, :28])
+    import torch
+
+    hdrs = torch.full((40 * len(ok) + 16,), SENT, dtype=torch.uint8, device="cuda:0")
+    ueng.tcp_wrap_headers(_t(pbuf) if pbuf.size else torch.zeros(16, dtype=torch.uint8, device="cuda:0"),
+                          _t(msgs.reshape(-1)), hdrs, n=len(ok), offsets=_t(poff))
+    got = hdrs.cpu().numpy()[:40 * len(ok)].reshape(-1, 40)
+    want = np.frombuffer(b"".join(d[:40] for d in ok), np.uint8).reshape(-1, 40)
+    assert (got == want).all(), np.flatnonzero((got != want).any(axis=1))[:8]
+
+
+def test_call_level_cases(ueng):
+    import torch
+
+    from tcpip_network_protocol_stack_amd._lib import IcsumError
+
+    eng, lib = ueng, ueng.lib
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    a, b = mixed(0xCA11, 200), mixed(0xCA12, 200)
+    (abuf, aoff), (bbuf, boff) = pack(a), pack(b)
+    da, db, dao, dbo = _t(abuf), _t(bbuf), _t(aoff), _t(boff)
+    # n = 0 launches nothing
+    before = eng.dispatch_info()["kernel"]
+    assert lib.ics_tcp_unwrap_batch(eng.ctx, None, None, 0, 0, 0, None, None, stream) == 0
+    assert eng.dispatch_info()["kernel"] == before
+    # a null d_status (context scratch), called directly
+    recs = torch.full((40 * 200 + 8,), SENT, dtype=torch.uint8, device="cuda:0")
+    assert lib.ics_tcp_unwrap_batch(eng.ctx, da.data_ptr(), dao.data_ptr(), 0, 0, 200, recs.data_ptr(), None,
+                                    stream) == 0
+    assert (recs.cpu().numpy()[:8000].reshape(200, 40) == expected(a)).all() and (recs.cpu().numpy()[8000:] == SENT).all()
+    # null and misaligned record arrays, a null datagram buffer
+    clean = torch.full((40 * 200 + 8,), SENT, dtype=torch.uint8, device="cuda:0")
+    assert lib.ics_tcp_unwrap_batch(eng.ctx, da.data_ptr(), dao.data_ptr(), 0, 0, 200, None, None, stream) == -1
+    assert b"null record array" in lib.ics_last_error()
+    for k in (1, 2, 3):
+        with pytest.raises(IcsumError, match="not 4-byte aligned"):
+            eng.tcp_unwrap_batch(da, n=200, offsets=dao, recs=clean[k:])
+    assert lib.ics_tcp_unwrap_batch(eng.ctx, None, dao.data_ptr(), 0, 0, 200, clean.data_ptr(), None, stream) == -1
+    assert b"null datagram buffer" in lib.ics_last_error()
+    assert (clean.cpu().numpy() == SENT).all()
+    # two calls on one stream into one record array: the second wins
+    eng.tcp_unwrap_batch(da, n=200, offsets=dao, recs=recs)
+    eng.tcp_unwrap_batch(db, n=200, offsets=dbo, recs=recs)
+    assert (recs.cpu().numpy()[:8000].reshape(200, 40) == expected(b)).all()
+    # a non-default stream, read on that stream
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        recs2 = torch.full((40 * 200,), SENT, dtype=torch.uint8, device="cuda:0")
+        st2 = torch.full((200,), 0x5A, dtype=torch.uint8, device="cuda:0")
+        eng.tcp_unwrap_batch(da, n=200, offsets=dao, recs=recs2, status=st2, stream=s)
+        host = torch.empty(40 * 200, dtype=torch.uint8, pin_memory=True)
+        host.copy_(recs2, non_blocking=True)
+        s.synchronize()
+    assert (host.numpy().reshape(200, 40) == expected(a)).all()
+    assert (st2.cpu().numpy() == expected(a)[:, 36]).all()
+    assert eng.dispatch_info()["kernel"] == "unwrap"
+
+
+def test_verify_is_unchanged_around_an_unwrap_call(ueng):
+    """ICS_MODE_VERIFY through ics_ipv4_tcp_batch before and after an unwrap
+    call on the same context: identical outputs"""
+    dgrams = mixed(0x5AFE, 1500)
+    buf, off = pack(dgrams, lead=1)
+    d, do = _t(buf), _t(off)
+    n = len(dgrams)
+    before = [x.cpu().numpy().copy() for x in ueng.ipv4_tcp_batch(d, 1, n=n, offsets=do)]
+    kernel = ueng.dispatch_info()["kernel"]
+    recs, _ = run(ueng, d, n, offsets=do)
+    after = [x.cpu().numpy() for x in ueng.ipv4_tcp_batch(d, 1, n=n, offsets=do)]
+    assert ueng.dispatch_info()["kernel"] == kernel
+    for x, y in zip(before, after):
+        assert (x == y).all()
+    assert (after[2] == recs[:, 36]).all()
+    assert (after[2] == [verify_status(x) for x in dgrams]).all()
+
+
+# ------------------------------------------------------------ host variant --
+def _host_engine(slots, debug):
+    env = {"ICSUM_HOST_SLOT_MB": "1", "ICSUM_HOST_SLOTS": str(slots)}
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        gen = engine_with(debug=debug)
+        eng = next(gen)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    return gen, eng
+
+
+@pytest.fixture(scope="module", params=[(2, False), (4, False), (2, True)], ids=["slots2", "slots4", "slots2-debug"])
+def heng(request):
+    gen, eng = _host_engine(*request.param)
+    yield eng
+    next(gen, None)
+
+
+def _host(buf, pinned):
+    import torch
+
+    h = torch.empty(buf.size + 16, dtype=torch.uint8, pin_memory=pinned).numpy()
+    h[:buf.size] = buf
+    h[buf.size:] = SENT
+    return h
+
+
+def _host_case(eng, buf, n, chunks, tag, **kw):
+    """the host call from pageable and from page-locked memory against the
+    device call's records; `chunks`: (zero-copy calls, DMA'd chunks) expected"""
+    from tcpip_network_protocol_stack_amd.engine import TCP_RX_DTYPE
+
+    dkw = {k: (_t(v) if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
+    want, _ = run(eng, _t(buf), n, **dkw)
+    for pinned in (False, True):
+        h = _host(buf, pinned)
+        recs = np.full(40 * (n + 2), SENT, np.uint8).view(TCP_RX_DTYPE)
+        a = eng.dispatch_info()
+        eng.tcp_unwrap_batch_host(h, n, recs=recs, **kw)
+        b = eng.dispatch_info()
+        assert b["kernel"] == "unwrap"
+        assert (b["host_zero_copy"] - a["host_zero_copy"], b["host_dma_chunks"] - a["host_dma_chunks"]) == chunks, tag
+        got = recs.view(np.uint8).reshape(n + 2, 40)
+        assert (got[n:] == SENT).all(), tag
+        bad = np.flatnonzero((got[:n] != want).any(axis=1))
+        assert bad.size == 0, (tag, pinned, bad[:8].tolist())
+        assert (h[:buf.size] == buf).all() and (h[buf.size:] == SENT).all(), tag
+    return want
+
+
+def test_host_chunk_cuts_and_slot_turn(heng):
+    """2100 x 1500 B with 1 MiB slots: chunks of 699 datagrams, more chunks
+    than slots (a slot turn with two slots)"""
+    rng = random.Random(0x40057)
+    pool = [make_dgram(rng, 1500, rng.choice(HLENS), rng.choice(DOFFS)) for _ in range(48)]
+    dgrams = [pool[rng.randrange(48)] for _ in range(2100)]
+    buf = np.frombuffer(b"".join(dgrams), np.uint8)
+    want = _host_case(heng, buf, 2100, (0, 4), "stride 1500", stride=1500, dgram_len=1500)
+    assert (want == expected(dgrams)).all()
+    off = np.arange(2101, dtype=np.uint64) * np.uint64(1500)
+    _host_case(heng, buf, 2100, (0, 4), "offsets 1500", offsets=off)
+
+
+def test_host_count_cut(ueng):
+    """2^18 + 3 datagrams of 40 bytes through the default 32 MiB slots: 10 MiB
+    cut by count at kWrapSlotSegs, three datagrams in the second chunk"""
+    n = hc.K_WRAP_SLOT_SEGS + 3
+    assert n == (1 << 18) + 3
+    rng = random.Random(0xC027)
+    pool = [make_dgram(rng, 40, 5, rng.choice([5, 5, 5, 4])) for _ in range(256)]
+    pool = np.frombuffer(b"".join(pool), np.uint8).reshape(256, 40)
+    pick = np.random.default_rng(0xC027).integers(0, 256, n)
+    pick[-3:] = [i for i in range(256) if verify_status(pool[i].tobytes()) & PARSED == PARSED][:3]  # behind the cut
+    buf = pool[pick].reshape(-1).copy()
+    want = _host_case(ueng, buf, n, (0, 2), "count cut", stride=40, dgram_len=40)
+    assert (want[-3:] == expected([pool[i].tobytes() for i in pick[-3:]])).all()
+    parsed = (want[:, 36] & PARSED) == PARSED
+    assert parsed[-3:].all() and parsed.mean() > 0.5 and not parsed.all()
+
+
+def test_host_zero_copy_and_above(heng):
+    """a mixed batch small enough to be read in place (one chunk, page-locked
+    or staged into the pinned slot) and one above the slot size"""
+    small = mixed(0x2C, 300)
+    buf, off = pack(small)
+    assert buf.size < (1 << 20)
+    want = _host_case(heng, buf, 300, (1, 0), "zero-copy", offsets=off)
+    assert (want == expected(small)).all()
+    big = mixed(0x2D, 14000)
+    buf, off = pack(big)
+    chunks = hc.counters(hc.plan(14000, off, hc.S, hc.K_WRAP_SLOT_SEGS, False))
+    assert buf.size > 2 * hc.S and chunks[0] == 0 and chunks[1] >= 3
+    want = _host_case(heng, buf, 14000, chunks, "staged", offsets=off)
+    assert (want == expected(big)).all()
+    # one datagram, and the errors
+    from tcpip_network_protocol_stack_amd._lib import IcsumError
+
+    one = make_dgram(random.Random(1), 60, 5, 5, fix=1.0, flip=0.0)
+    _host_case(heng, np.frombuffer(one, np.uint8), 1, (1, 0), "one", stride=60, dgram_len=60)
+    with pytest.raises(IcsumError, match="null record array"):
+        heng._check(heng.lib.ics_tcp_unwrap_batch_host(heng.ctx, buf.ctypes.data, off.ctypes.data, 0, 0, 14000, None))
+    bad = off.copy()
+    bad[100] = bad[99] - np.uint64(1)
+    with pytest.raises(IcsumError, match=r"not monotone: offsets\[99\] > offsets\[100\]"):
+        heng.tcp_unwrap_batch_host(buf, 14000, offsets=bad)
+    assert heng.lib.ics_tcp_unwrap_batch_host(heng.ctx, None, None, 0, 0, 0, None) == 0
+    _host_case(heng, np.frombuffer(one, np.uint8), 1, (1, 0), "after the errors", stride=60, dgram_len=60)
+
+
+def test_batch_engine_unwrap_records():
+    """csrc/host/tests/unwrap_records_test.cpp: BatchEngine::unwrap_records
+    against unwrap_packed and the per-object unwrap_tcp_in_ip on the same
+    wires, message for message — a listening adapter that connects on the
+    third datagram, a connected one with each gate wrong in turn"""
+    import subprocess
+
+    from conftest import ROOT
+
+    exe = os.path.join(ROOT, "tcpip_network_protocol_stack_amd", "csrc", "host", "build", "unwrap_records_test")
+    assert os.path.exists(exe), "build() did not produce unwrap_records_test"
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr[-3000:]
+    assert out.stdout.startswith("OK:")
