@@ -222,8 +222,10 @@ int ics_route_table_stats(ics_route_table* tbl, ics_route_stats_t* stats);
  * tables (least recently used replaced) and uploads a table's image on
  * `stream` on its first use after a change; that upload synchronises
  * `stream`, every other call only enqueues.  Calls on one stream see table
- * changes in order; changing a table while a launch on ANOTHER stream still
- * uses it is the caller's race. */
+ * changes in order.  A launch already enqueued, on any stream, keeps the
+ * image it was given: the upload that replaces an image (a changed table, or
+ * another table taking its place) first waits for every such launch.  Calls
+ * that read an unchanged image never wait for each other. */
 #define ICS_NO_ROUTE 0xFFFFFFFFu
 int ics_route_lookup_batch(ics_ctx* ctx, ics_route_table* tbl, const uint32_t* d_addrs, uint64_t n,
                            uint32_t* d_iface, uint32_t* d_next_hop, void* stream);

@@ -244,8 +244,9 @@ struct ics_ctx {
   // images of up to kRouteSlots tables, keyed by the table's id and generation
   // (never by pointer: a destroyed table's address is reused), the least
   // recently used slot replaced.  A slot's image is uploaded on the call's
-  // stream when the generation differs (the upload waits for the slot's last
-  // launch and synchronises the stream).  Buffers only grow, by doubling; an
+  // stream when the generation differs (the upload waits for the last launch
+  // of every stream that read the slot, RouteSlot::readers, and synchronises
+  // the stream).  Buffers only grow, by doubling; an
   // outgrown one is kept until ics_destroy (hipFree synchronises the whole
   // device).  route_mu is held from the slot lookup through the
   // launch, so no other thread replaces the slot in between.
@@ -258,9 +259,19 @@ struct ics_ctx {
     // (csrc/icsum_neigh.h): its identity entries and hash slots
     uint64_t nwords = 0;
     uint32_t nrecs = 0;
-    uint64_t used = 0;        // LRU clock
-    hipEvent_t ev = nullptr;  // recorded behind the last launch that read the slot
-    bool launched = false;
+    uint64_t used = 0;  // LRU clock
+    // One (stream, event) pair per stream that has launched a read of the
+    // slot, the event recorded behind that stream's last such launch: an
+    // event only remembers its last record, so one event for the slot would
+    // forget a long launch on stream A as soon as stream B launched.  Readers
+    // never wait for each other; a replacement waits for every pair.  A pair
+    // whose event has completed is taken over by the next new stream, so the
+    // set stays as small as the number of streams in flight at once.
+    struct Reader {
+      hipStream_t st = nullptr;
+      hipEvent_t ev = nullptr;
+    };
+    std::vector<Reader> readers;
   };
   RouteSlot route_slot[kRouteSlots];
   // neighbour images (ics_frame_recv_batch, ics_router_frames), kept the same

@@ -38,7 +38,8 @@ int image_slot(ics_ctx* ctx, ics_ctx::RouteSlot (&slots)[ics_ctx::kRouteSlots], 
   }
   if (slot->id != id || slot->gen != gen) {
     slot->id = 0;  // not trusted until the upload has landed
-    if (slot->launched) ICS_HIP(hipEventSynchronize(slot->ev));  // a launch on another stream may still read it
+    // launches on any stream may still read it: every stream's last one is behind its pair's event
+    for (auto& r : slot->readers) ICS_HIP(hipEventSynchronize(r.ev));
     if (need > slot->cap) {
       const size_t cap = (std::max(need, 2 * slot->cap) + (size_t(2) << 20) - 1) & ~((size_t(2) << 20) - 1);
       void* p = nullptr;
@@ -55,7 +56,6 @@ int image_slot(ics_ctx* ctx, ics_ctx::RouteSlot (&slots)[ics_ctx::kRouteSlots], 
     slot->nrecs = b;
   }
   slot->used = ++ctx->route_clock;
-  if (!slot->ev) ICS_HIP(hipEventCreateWithFlags(&slot->ev, hipEventDisableTiming));
   *out = slot;
   return ICS_OK;
 }
@@ -76,14 +76,32 @@ int neigh_slot_for(ics_ctx* ctx, ics_neigh_table* tbl, hipStream_t st, ics_ctx::
                     v.nslots, st, out);
 }
 
-// the launch that read the slot is behind its event, or nothing may replace the image under it
+// The launch that read the slot is behind the event of its stream's pair, or
+// nothing may replace the image under it.  A stream new to the slot takes over
+// a pair whose event has completed, else a new pair; no reader waits for
+// another.
 void slot_launched(ics_ctx::RouteSlot* slot, hipStream_t st) {
-  if (hipEventRecord(slot->ev, st) == hipSuccess) {
-    slot->launched = true;
-  } else {
-    (void)hipStreamSynchronize(st);
-    slot->launched = false;
+  ics_ctx::RouteSlot::Reader* r = nullptr;
+  for (auto& x : slot->readers)
+    if (x.st == st) r = &x;
+  if (!r)
+    for (auto& x : slot->readers)
+      if (hipEventQuery(x.ev) == hipSuccess) {
+        r = &x;
+        break;
+      }
+  if (!r) {
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
+      slot->readers.push_back({st, ev});
+      r = &slot->readers.back();
+    }
   }
+  if (r && hipEventRecord(r->ev, st) == hipSuccess) {
+    r->st = st;
+    return;
+  }
+  (void)hipStreamSynchronize(st);  // no event behind this launch: it is not in flight any more instead
 }
 }  // namespace
 
@@ -125,9 +143,11 @@ int frames_device(ics_ctx* ctx, ics_route_table* routes, ics_neigh_table* neigh,
 void free_routes(ics_ctx* ctx) {
   for (auto* slots : {&ctx->route_slot, &ctx->neigh_slot})
     for (auto& s : *slots) {
-      if (s.launched) (void)hipEventSynchronize(s.ev);
+      for (auto& r : s.readers) {
+        (void)hipEventSynchronize(r.ev);
+        (void)hipEventDestroy(r.ev);
+      }
       if (s.d) (void)hipFree(s.d);
-      if (s.ev) (void)hipEventDestroy(s.ev);
       s = {};
     }
   for (void* p : ctx->route_retired) (void)hipFree(p);

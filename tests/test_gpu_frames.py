@@ -483,3 +483,69 @@ def test_more_tables_than_image_slots_and_wrapping_chains(hop):
     r1.close()
     for t in tables:
         t.close()
+
+
+# --------------------------------------------------------- batch-size sweep --
+@pytest.fixture(scope="module")
+def sweep_burst():
+    """513 frames of the length mix, packed, with the whole hop's expectation: (frames, ins, buf, off)"""
+    import periodic as P
+
+    frames, ins = make_burst(0x5EE9, mixed_lengths(0x5EE9, P.SWEEP_MAX))
+    return (frames, ins) + _pack(frames)
+
+
+def test_frame_recv_every_batch_size(hop, sweep_burst):
+    """n = 0..130, 255..257, 511..513 on one uploaded batch: a partial last wave of every size, the block edge"""
+    import torch
+    import periodic as P
+
+    eng, routes, neigh, router, rneigh = hop
+    frames, ins, buf, off = sweep_burst
+    st, _, _, _ = expect(frames, ins, router, rneigh)
+    assert (st & FR_DGRAM != 0).any() and (st & FR_ARP_OK != 0).any() and (st == 0).any()
+    d, doff, dins = _t(buf), _t(off), _t(ins)
+    P.sweep_sizes(lambda n, o: eng.frame_recv(neigh, d, n=n, offsets=doff, in_ifaces=dins, status=o[0]),
+                  [(torch.uint8, 1, 0x5A)], [st & 0xF8])
+    assert (d.cpu().numpy() == buf).all()
+
+
+def test_router_frames_every_batch_size(hop, sweep_burst):
+    import torch
+    import periodic as P
+
+    eng, routes, neigh, router, rneigh = hop
+    frames, ins, buf, off = sweep_burst
+    st, fi, fh, rec = expect(frames, ins, router, rneigh)
+    assert (st & FR_RESOLVED != 0).any() and ((st & RT_FORWARD != 0) & (st & RT_ROUTED == 0)).any()
+    d, doff, dins = _t(buf), _t(off), _t(ins)
+    P.sweep_sizes(lambda n, o: eng.router_frames(routes, neigh, d, n=n, offsets=doff, in_ifaces=dins, hdrs=o[0],
+                                                 status=o[1], iface=o[2], next_hop=o[3]),
+                  [(torch.uint8, 36, 0xA5), (torch.uint8, 1, 0x5A), (torch.int32, 1, 0x25A5A5A5),
+                   (torch.int32, 1, 0x25A5A5A5)], [rec, st, fi, fh])
+    assert (d.cpu().numpy() == buf).all()
+
+
+# ------------------------------------------------------------ shape lattice --
+def test_shape_lattice(hop):
+    """lattice_headers.py: every length class at every start residue mod 16 (one to four blocks held, the
+    load clamped at the last block or not), 80 packed batches with a third of the targets ending the allocation
+    in turn; both calls, every byte of every output, the frames untouched (test_shape_lattice_headers.py proves
+    the coverage on the CPU)"""
+    import lattice_headers as LH
+
+    eng, routes, neigh, router, rneigh = hop
+    targets, tins, res = LH.frame_targets()
+    seen = []
+    for b in range(LH.n_batches(len(targets))):
+        items, off, which = LH.batch(targets, res, b, seed=1)
+        ins = np.where(which >= 0, tins[np.maximum(which, 0)], b % 4).astype(np.uint32)
+        buf = np.frombuffer(b"".join(items), np.uint8).copy()
+        assert buf.size == int(off[-1])
+        d = _t(buf)
+        seen.append(check_hop(eng, routes, neigh, router, rneigh, items, ins, d, len(items), ("lattice", b),
+                              offsets=_t(off)))
+        assert (d.cpu().numpy() == buf).all(), b
+    st = np.concatenate(seen)
+    for bit in (FR_RESOLVED, RT_ROUTED, RT_FORWARD, FR_DGRAM, FR_IPV4, FR_FOR_US, FR_ARP, FR_ARP_OK):
+        assert (st & bit != 0).any(), bit

@@ -420,3 +420,231 @@ def test_offsets_wrap_across_2g_4g(weng4, orc, apart):
                 assert (got == buf).all()
     del t
     torch.cuda.empty_cache()
+
+
+# ------------------------------- route, frame and unwrap families (tables) ---
+# The address arithmetic of k_frame, k_tcp_unwrap and the fused router kernels
+# (`s & ~15`, `alast`, `dg + s + hl`, `frame + 14`) is written in 64 bits;
+# these cases hold it there.  Inputs are periodic.py's K = 4099 items (every
+# status class, asserted), expectations the restatements (frame_ref /
+# route_ref / unwrap_ref); a fixed-stride batch repeats the items over the
+# whole buffer and is compared in full on the device — the windows around each
+# boundary and both ends included — an offsets batch is the K items placed
+# with _place.  Every output is sentinel-filled with 64 elements behind it.
+@pytest.fixture(scope="module")
+def hop4(engine):
+    """(RouteTable, NeighTable, RefRouter, RefNeigh): test_gpu_frames' tables"""
+    import test_gpu_frames as F
+    from frame_ref import RefNeigh
+    from route_ref import RefRouter, fill
+    from tcpip_network_protocol_stack_amd.engine import NeighTable, RouteTable
+
+    routes, neigh = fill(RouteTable(), F.ROUTES), F._fill_neigh(NeighTable())
+    yield routes, neigh, RefRouter(F.ROUTES), F._fill_neigh(RefNeigh())
+    _torch().cuda.synchronize()
+    routes.close()
+    neigh.close()
+
+
+STRIDE_T = 1024  # item 2^21 starts on 2^31, item 2^22 on 2^32
+
+
+def _fill_periodic(t, items, rng):
+    """the K items at the starts of K slots of 1024 random bytes, repeated over the whole buffer"""
+    import periodic as P
+
+    block = rng.integers(0, 256, (P.K, STRIDE_T), dtype=np.uint8)
+    for i, x in enumerate(items):
+        block[i, :len(x)] = np.frombuffer(x, np.uint8)
+    blk = _dev(block.reshape(-1))
+    per = blk.numel()
+    full = BIG // per
+    t[:full * per].view(full, per).copy_(blk.view(1, per).expand(full, per))
+    t[full * per:] = blk[:BIG - full * per]
+    return blk
+
+
+def _out(n, dtype, width=1):
+    import periodic as P
+
+    torch = _torch()
+    value = {torch.int32: 0x25A5A5A5, torch.uint8: 0xA5 if width > 1 else 0x5A}[dtype]
+    return P.sentinel(n * width, dtype, value) + (value,)
+
+
+def _full(out, n, want, width, tag):
+    """the output's first n items equal the K-item expectation repeated, its tail is untouched"""
+    import periodic as P
+
+    torch = _torch()
+    whole, _, value = out
+    exp = P.tile(_dev(np.ascontiguousarray(want).reshape(-1)), n, width)
+    got = whole[:n * width]
+    if not torch.equal(got, exp):
+        j = int((got != exp).nonzero()[0])
+        raise AssertionError(f"{tag}: item {j // width} (byte offset {j // width * STRIDE_T:#x}) differs: "
+                             f"{int(got[j]):#x}, want {int(exp[j]):#x}")
+    assert P.tail_untouched(whole, n * width, value), tag
+
+
+def test_fixed_stride_tables_across_2g_4g(engine, hop4):
+    """frame_recv, router_frames, router_route_headers, the in-place router_route_batch and tcp_unwrap_batch over
+    1024-byte slots spanning the whole buffer: a frame / datagram starts exactly on 2^31 and on 2^32"""
+    import periodic as P
+    import random
+    import test_gpu_frames as F
+    from unwrap_ref import make_dgram
+
+    torch = _torch()
+    routes, neigh, router, rneigh = hop4
+    rng = np.random.default_rng(0x4F1)
+    t = _fresh(engine, SEED + 7)
+    n = BIG // STRIDE_T
+    assert n > B32 // STRIDE_T + 1000 and B31 % STRIDE_T == 0
+    u8, i32 = torch.uint8, torch.int32
+    # frames
+    frames, ins = P.frame_items(0x4F2)
+    st, fi, fh, rec = F.expect(frames, ins, router, rneigh)
+    P.assert_frame_classes(st)
+    _fill_periodic(t, frames, rng)
+    dins = P.tile(_dev(ins), n)
+    kw = dict(n=n, stride=STRIDE_T, frame_len=P.FRAME_LEN, in_ifaces=dins)
+    o = _out(n, u8)
+    engine.frame_recv(neigh, t, status=o[1], **kw)
+    _full(o, n, st & 0xF8, 1, "frame_recv status")
+    o_hd, o_st, o_f, o_h = _out(n, u8, 36), _out(n, u8), _out(n, i32), _out(n, i32)
+    engine.router_frames(routes, neigh, t, hdrs=o_hd[1], status=o_st[1], iface=o_f[1], next_hop=o_h[1], **kw)
+    _full(o_st, n, st, 1, "router_frames status")
+    _full(o_f, n, fi, 1, "router_frames iface")
+    _full(o_h, n, fh, 1, "router_frames next_hop")
+    _full(o_hd, n, rec, 36, "router_frames records")
+    del o, o_hd
+    # datagrams: the frames behind their Ethernet header
+    dgrams = [f[14:] for f in frames]
+    st, fi, fh, hd, after = P.route_expect(dgrams, router)
+    P.assert_route_classes(st)
+    blk = _fill_periodic(t, dgrams, rng)
+    kw = dict(n=n, stride=STRIDE_T, dgram_len=P.FRAME_LEN - 14)
+    o_hd, o_st, o_f, o_h = _out(n, u8, 20), _out(n, u8), _out(n, i32), _out(n, i32)
+    engine.router_route_headers(routes, t, hdrs=o_hd[1], status=o_st[1], iface=o_f[1], next_hop=o_h[1], **kw)
+    for o, w, width, tag in ((o_hd, hd, 20, "headers"), (o_st, st, 1, "status"), (o_f, fi, 1, "iface"),
+                             (o_h, fh, 1, "next_hop")):
+        _full(o, n, w, width, "router_route_headers " + tag)
+    per = blk.numel()
+    o_st, o_f, o_h = _out(n, u8), _out(n, i32), _out(n, i32)
+    engine.router_route_batch(routes, t, status=o_st[1], iface=o_f[1], next_hop=o_h[1], **kw)
+    for o, w, tag in ((o_st, st, "status"), (o_f, fi, "iface"), (o_h, fh, "next_hop")):
+        _full(o, n, w, 1, "router_route_batch " + tag)
+    # the bytes the in-place call leaves: the forwarded header over each slot's first 20 bytes, nothing else
+    want = blk.view(P.K, STRIDE_T).clone()
+    want[:, :P.FRAME_LEN - 14] = _dev(np.frombuffer(b"".join(after), np.uint8)).view(P.K, -1)
+    full = BIG // per
+    assert torch.equal(t[:full * per].view(full, per), want.view(1, per).expand(full, per)), "in-place datagram bytes"
+    assert torch.equal(t[full * per:], want.view(-1)[:BIG - full * per])
+    # unwrap: 60-byte datagrams of every header shape
+    r = random.Random(0x4F3)
+    dgrams = [make_dgram(r, 60, r.choice(P.HLENS + [4]), r.choice(P.DOFFS)) for _ in range(P.K)]
+    want = P.unwrap_expect(dgrams)
+    stu = want[:, 36]
+    assert (stu == 0x0F).any() and (stu == 0x07).any() and (stu & 1 == 0).any() and ((stu & 7 == 7).sum() > 1000)
+    _fill_periodic(t, dgrams, rng)
+    o_rec, o_st = _out(n, u8, 40), _out(n, u8)
+    engine.tcp_unwrap_batch(t, n=n, stride=STRIDE_T, dgram_len=60, recs=o_rec[1], status=o_st[1])
+    _full(o_rec, n, want, 40, "unwrap records")
+    _full(o_st, n, stu.copy(), 1, "unwrap status")
+    del t
+    torch.cuda.empty_cache()
+
+
+def _middle(items, at_least):
+    """the items with one of at least `at_least` bytes in the middle (the one _place puts across the boundary)"""
+    mid = len(items) // 2
+    k = next(i for i in range(mid, len(items)) if len(items[i]) >= at_least)
+    items = list(items)
+    items[mid], items[k] = items[k], items[mid]
+    return items
+
+
+def test_offsets_tables_across_2g_4g(engine, hop4):
+    """packed frames / datagrams with item K // 2 straddling 2^31 / 2^32 (starting 5 bytes below) or starting on it"""
+    import periodic as P
+    import test_gpu_frames as F
+    from unwrap_ref import PARSED
+
+    torch = _torch()
+    routes, neigh, router, rneigh = hop4
+    u8, i32 = torch.uint8, torch.int32
+    n = P.K
+    frames, ins = F.make_burst(0x4F5, F.mixed_lengths(0x4F5, n))
+    frames = _middle(frames, 60)
+    st, fi, fh, rec = F.expect(frames, ins, router, rneigh)
+    P.assert_frame_classes(st)
+    dgrams = _middle(P.dgram_items(0x4F6), 40)
+    rst, rfi, rfh, rhd, after = P.route_expect(dgrams, router)
+    P.assert_route_classes(rst)
+    udg = _middle(P.unwrap_items(0x4F7), 60)
+    urec = P.unwrap_expect(udg)
+    P.assert_unwrap_classes(urec, udg)
+    t = _fresh(engine, SEED + 8)
+    dins = _dev(ins)
+
+    def same(out, want, width, tag):
+        whole, _, value = out
+        got = whole.cpu().numpy()
+        want = np.ascontiguousarray(want).reshape(-1)
+        g = got[:n * width].view(np.uint32) if got.dtype == np.int32 else got[:n * width]
+        bad = np.flatnonzero(g != want)
+        assert bad.size == 0, (tag, (bad[:8] // width).tolist())
+        assert (got[n * width:] == value).all(), tag
+
+    for bnd in BOUNDS:
+        for how in ("straddle", "on"):
+            tag = (hex(bnd), how)
+            buf, rel = P.pack(frames)
+            off = _place(t, np.concatenate([buf, np.zeros(16, np.uint8)]), rel, bnd, how)
+            assert off[n // 2] < bnd + (how == "on") <= off[n // 2 + 1] and off[0] < bnd < off[-1]
+            doff = _dev(off)
+            o = _out(n, u8)
+            engine.frame_recv(neigh, t, n=n, offsets=doff, in_ifaces=dins, status=o[1])
+            same(o, st & 0xF8, 1, tag + ("frame_recv",))
+            o_hd, o_st, o_f, o_h = _out(n, u8, 36), _out(n, u8), _out(n, i32), _out(n, i32)
+            engine.router_frames(routes, neigh, t, n=n, offsets=doff, in_ifaces=dins, hdrs=o_hd[1], status=o_st[1],
+                                 iface=o_f[1], next_hop=o_h[1])
+            for o, w, width in ((o_hd, rec, 36), (o_st, st, 1), (o_f, fi, 1), (o_h, fh, 1)):
+                same(o, w, width, tag + ("router_frames",))
+            assert (_host(t, int(off[0]), int(off[-1])) == buf).all(), tag  # the frames are only read
+
+            buf, rel = P.pack(dgrams)
+            off = _place(t, np.concatenate([buf, np.zeros(16, np.uint8)]), rel, bnd, how)
+            assert off[n // 2] < bnd + (how == "on") <= off[n // 2 + 1]
+            doff = _dev(off)
+            o_hd, o_st, o_f, o_h = _out(n, u8, 20), _out(n, u8), _out(n, i32), _out(n, i32)
+            engine.router_route_headers(routes, t, n=n, offsets=doff, hdrs=o_hd[1], status=o_st[1], iface=o_f[1],
+                                        next_hop=o_h[1])
+            for o, w, width in ((o_hd, rhd, 20), (o_st, rst, 1), (o_f, rfi, 1), (o_h, rfh, 1)):
+                same(o, w, width, tag + ("router_route_headers",))
+            assert (_host(t, int(off[0]), int(off[-1])) == buf).all(), tag
+            o_st, o_f, o_h = _out(n, u8), _out(n, i32), _out(n, i32)
+            engine.router_route_batch(routes, t, n=n, offsets=doff, status=o_st[1], iface=o_f[1], next_hop=o_h[1])
+            for o, w in ((o_st, rst), (o_f, rfi), (o_h, rfh)):
+                same(o, w, 1, tag + ("router_route_batch",))
+            assert (_host(t, int(off[0]), int(off[-1])) == P.pack(after)[0]).all(), tag  # the forwarded headers in place
+            assert (_host(t, int(off[-1]), int(off[-1]) + 16) == 0).all(), tag
+
+            buf, rel = P.pack(udg)
+            off = _place(t, np.concatenate([buf, np.zeros(16, np.uint8)]), rel, bnd, how)
+            assert off[n // 2] < bnd + (how == "on") <= off[n // 2 + 1]
+            for with_status in (True, False):
+                o_rec, o_st = _out(n, u8, 40), _out(n, u8)
+                engine.tcp_unwrap_batch(t, n=n, offsets=_dev(off), recs=o_rec[1], status=o_st[1] if with_status else None)
+                same(o_rec, urec, 40, tag + ("unwrap", with_status))
+                if with_status:
+                    same(o_st, urec[:, 36].copy(), 1, tag + ("unwrap status",))
+            # pay_off / pay_len stay datagram-relative: never the 2^31 / 2^32 byte offsets of the batch
+            got = o_rec[0][:n * 40].cpu().numpy().reshape(n, 40)
+            ok = (got[:, 36] & PARSED) == PARSED
+            po, pl = got[:, 28:32].copy().view("<u4")[:, 0], got[:, 32:36].copy().view("<u4")[:, 0]
+            lens = np.array([len(d) for d in udg])
+            assert ok[n // 2 - 50:n // 2 + 50].any() and (po[ok] <= lens[ok]).all() and (po[ok] + pl[ok] == lens[ok]).all()
+    del t
+    torch.cuda.empty_cache()

@@ -337,3 +337,40 @@ def test_more_tables_than_image_slots(rt):
     assert (_u32(f) == wf).all() and (_u32(h) == wh).all()
     for t in tables:
         t.close()
+
+
+# --------------------------------------------------------- batch-size sweep --
+def test_lookup_every_batch_size(rt):
+    """n = 0..130, 255..257, 511..513 on one uploaded batch: a partial last wave of every size, the block edge"""
+    import torch
+    import periodic as P
+
+    eng, table = rt
+    rng = np.random.default_rng(0x5EE9)
+    addrs = np.concatenate([POOL, rng.integers(0, 2**32, P.SWEEP_MAX, dtype=np.uint64).astype(np.uint32)])
+    addrs = addrs[rng.permutation(addrs.size)][:P.SWEEP_MAX]
+    m, wf, wh = REF.answers(addrs)
+    assert 0 < m[:64].sum() < 64
+    d = _t(addrs)
+    P.sweep_sizes(lambda n, o: eng.route_lookup_batch(table, d, n=n, iface=o[0], next_hop=o[1]),
+                  [(torch.int32, 1, 0x25A5A5A5)] * 2, [wf, wh])
+
+
+def test_fused_headers_every_batch_size(rt, arena):
+    """router_route_headers (two lanes per datagram: 32 datagrams a wave, 128 a block) at the same sizes, on the
+    first n datagrams of the shared arena, against the restatement"""
+    import torch
+    import periodic as P
+
+    eng, table = rt
+    buf, off, _ = arena
+    n = P.SWEEP_MAX
+    dgrams = [buf[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)]
+    st, fi, fh, hd, _ = P.route_expect(dgrams, REF)
+    assert set(np.unique(st[:32])) == {0, 1, 3}
+    d, doff = _t(buf), _t(off[:n + 1])
+    P.sweep_sizes(lambda k, o: eng.router_route_headers(table, d, n=k, offsets=doff, hdrs=o[0], status=o[1], iface=o[2],
+                                                        next_hop=o[3]),
+                  [(torch.uint8, 20, 0xA5), (torch.uint8, 1, 0x5A), (torch.int32, 1, 0x25A5A5A5),
+                   (torch.int32, 1, 0x25A5A5A5)], [hd, st, fi, fh])
+    assert (d.cpu().numpy() == buf).all()

@@ -389,3 +389,43 @@ def test_batch_engine_unwrap_records():
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr[-3000:]
     assert out.stdout.startswith("OK:")
+
+
+def test_every_batch_size(ueng):
+    """n = 0..130, 255..257, 511..513 on one uploaded batch, with a status array and with the context's scratch:
+    a partial last wave of every size (the rows reused as the record staging area), the block edge"""
+    import torch
+    import periodic as P
+
+    dgrams = mixed(0x5EE9, P.SWEEP_MAX)
+    buf, off = pack(dgrams)
+    want = expected(dgrams)
+    parsed = (want[:, 36] & PARSED) == PARSED
+    assert parsed[:64].any() and not parsed[:64].all()
+    d, doff = _t(buf), _t(off)
+    P.sweep_sizes(lambda n, o: ueng.tcp_unwrap_batch(d, n=n, offsets=doff, recs=o[0], status=o[1]),
+                  [(torch.uint8, 40, SENT), (torch.uint8, 1, 0x5A)], [want, want[:, 36].copy()])
+    P.sweep_sizes(lambda n, o: ueng.tcp_unwrap_batch(d, n=n, offsets=doff, recs=o[0], status=None),
+                  [(torch.uint8, 40, SENT)], [want])
+    assert (d.cpu().numpy() == buf).all()
+
+
+def test_shape_lattice(ueng):
+    """lattice_headers.py: every length class at every start residue mod 16, header lengths 5 / 6 / 15 and data
+    offsets 4 / 5 / 6 / 15 on every class, the TCP header at every residue mod 4 on the options path; 75 packed
+    batches with a third of the targets ending the allocation in turn; all 40 bytes of every record, with a
+    status array and with the context's scratch, the datagrams untouched (test_shape_lattice_headers.py proves
+    the coverage on the CPU)"""
+    import lattice_headers as LH
+
+    targets, res, _ = LH.dgram_targets()
+    parsed = 0
+    for b in range(LH.n_batches(len(targets))):
+        items, off, _ = LH.batch(targets, res, b, seed=2)
+        buf = np.frombuffer(b"".join(items), np.uint8).copy()
+        assert buf.size == int(off[-1])
+        d = _t(buf)
+        want = check(ueng, items, d, ("lattice", b), offsets=_t(off))
+        parsed += int(((want[:, 36] & PARSED) == PARSED).sum())
+        assert (d.cpu().numpy() == buf).all(), b
+    assert parsed > 75 * 40
