@@ -8,7 +8,7 @@
 // compiled image (csrc/icsum_neigh.h) the kernel reads.
 #pragma once
 
-#include "icsum_ipv4.h"
+#include "icsum_hdrpass.h"
 #include "icsum_route.h"
 
 namespace icsum {
@@ -68,23 +68,12 @@ __device__ __forceinline__ bool neigh_find(const NeighImg& t, uint32_t f, uint32
   return false;
 }
 
-// A wave takes 64 consecutive frames per pass, in two phases.
-// Load: a frame's first 34 bytes (14 of Ethernet, then the IPv4 header or the
-// first 8 bytes of ARP) lie in at most four of the aligned 16-byte blocks that
-// hold the frame.  Four lanes per frame, lane j loading block j with ONE
-// dwordx4 load clamped at the frame's last block (a frame below 14 bytes, or
-// one past the batch, reads the zero pad): four load instructions per 64
-// frames, each touching 16 frames with 64 neighbouring bytes, and nothing
-// outside the blocks that hold the frame is read.  The blocks go to LDS, one
-// 17-dword row per frame.
-// Parse: ONE lane per frame.  It reads the ten dwords from the frame's start
-// dword on (LDS takes any dword address; the odd row length keeps 64 rows on
-// different banks), aligns them to the frame start (alignbyte by the start's
-// low two bits) and takes the header 14 bytes in by a fixed alignbyte of 2.
-// Every lane then works on a frame of its own: the route walk and the
-// neighbour probe are gathers of 64 lanes, and status / iface / next hop are
-// coalesced stores.  Decisions read only bytes the length check has shown to
-// exist: clamped blocks are never interpreted.
+// A header-only pass in rows (rows_load / row_take, icsum_hdrpass.h): a wave
+// takes 64 consecutive frames per pass.  A frame's first 34 bytes are 14 of
+// Ethernet, then the IPv4 header or the first 8 bytes of ARP; the parsing
+// lane takes the header 14 bytes in by a fixed alignbyte of 2.  Every lane
+// then works on a frame of its own: the route walk and the neighbour probe
+// are gathers of 64 lanes, and status / iface / next hop are coalesced stores.
 // (Shapes tried, 1 M x 1514 B, classification / whole hop: k_router_hdrs' two
 // lanes per frame with five dword loads each 59.1 / 86.1 us; four lanes per
 // frame with the dwordx4 load and the lookups on one lane in four 50.5 / 89.0
@@ -103,60 +92,27 @@ __global__ __launch_bounds__(kBlock) void k_frame(const uint8_t* __restrict__ fr
                                                   uint32_t* __restrict__ hdr_out, uint8_t* __restrict__ status,
                                                   const uint32_t* __restrict__ zpad, RouteImg rt, NeighImg nb,
                                                   uint32_t* __restrict__ rt_iface, uint32_t* __restrict__ rt_hop) {
-  constexpr uint32_t kPerWave = 64, kRec = 9, kRow = 17;
-  __shared__ uint32_t raw[kBlock / 64][kPerWave * kRow];
-  __shared__ uint32_t stage[kHop ? kBlock / 64 : 1][kHop ? kPerWave * kRec : 1];
+  constexpr uint32_t kRec = 9;
+  __shared__ uint32_t raw[kBlock / 64][kRowsPerWave * kRow];
+  __shared__ uint32_t stage[kHop ? kBlock / 64 : 1][kHop ? kRowsPerWave * kRec : 1];
   const uint32_t lane64 = threadIdx.x & 63u;
   uint32_t* const rw = raw[threadIdx.x >> 6];
   [[maybe_unused]] uint32_t* const sw = stage[kHop ? threadIdx.x >> 6 : 0];
   const uint64_t step = uint64_t(gridDim.x) * kBlock;
   const uint32_t bsh = frame_shift(fr);
-  fr -= bsh;  // 16-byte aligned: block bounds are multiples of 16 in this frame
+  fr -= bsh;
   for (uint64_t g0 = uint64_t(blockIdx.x) * kBlock; g0 < n; g0 += step) {  // uniform per block
-    const uint64_t wbase = g0 + (threadIdx.x >> 6) * kPerWave;
-    // ---- load: pass q brings frames wbase + 16 q .. + 15, four lanes each
-    u32x4 v[4];
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      const uint64_t j = wbase + 16u * q + (lane64 >> 2);
-      uint64_t s, e;
-      seg_bounds(offsets, stride, flen, j < n ? j : n - 1, s, e, bsh);
-      const bool eth = j < n && e - s >= 14;
-      const uint32_t blk = lane64 & 3u;
-      const uint64_t a0 = s & ~uint64_t(15), alast = (e - 1) & ~uint64_t(15);
-      const uint64_t at = a0 + 16u * blk < alast ? a0 + 16u * blk : alast;
-      const u32x4* src = eth ? reinterpret_cast<const u32x4*>(fr + at) : reinterpret_cast<const u32x4*>(zpad) + blk;
-#ifdef ICSUM_BOUNDS_CHECK
-      if (eth) ICS_CHECK16(src, fr + a0, fr + ((e + 15) & ~uint64_t(15)));
-#endif
-      v[q] = *src;
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      uint32_t* row = rw + (16u * q + (lane64 >> 2)) * kRow + 4u * (lane64 & 3u);
-      row[0] = v[q].x;
-      row[1] = v[q].y;
-      row[2] = v[q].z;
-      row[3] = v[q].w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint64_t wbase = g0 + (threadIdx.x >> 6) * kRowsPerWave;
+    rows_load<14>(fr, offsets, stride, flen, n, bsh, wbase, lane64, zpad, rw);
     // ---- parse: lane l has frame wbase + l
     const uint64_t i = wbase + lane64;
     const bool valid = i < n;
     uint64_t s, e;
     seg_bounds(offsets, stride, flen, valid ? i : n - 1, s, e, bsh);
-    const uint64_t len = e - s;
+    const uint64_t len = item_len(s, e);
     const bool eth = valid && len >= 14;
-    const uint32_t o = eth ? uint32_t(s & 15u) >> 2 : 0u, sh = eth ? uint32_t(s & 3u) : 0u;
-    uint32_t d[10];
-#pragma unroll
-    for (int w = 0; w < 10; ++w) d[w] = rw[lane64 * kRow + o + w];  // o + 9 <= 12
-    // f[k]: frame bytes 4k .. 4k + 3
     uint32_t f[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) f[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+    row_take(rw, lane64, eth, s, f);
     Hdr h;  // frame bytes 14 .. 33: the IPv4 header, or ARP's fixed fields in w[0], w[1]
 #pragma unroll
     for (int k = 0; k < 5; ++k) h.w[k] = __builtin_amdgcn_alignbyte(f[k + 4], f[k + 3], 2u);
@@ -172,19 +128,18 @@ __global__ __launch_bounds__(kBlock) void k_frame(const uint8_t* __restrict__ fr
     // ARPMessage::parse: 28 bytes and supported() — 00 01 08 00 | 06 04 00 op, op 1 or 2
     const bool arp_ok = arp && len >= 42 && h.w[0] == 0x00080100u &&
                         (h.w[1] == 0x01000406u || h.w[1] == 0x02000406u);
-    const uint32_t ver = h.byte(0) >> 4, hlen = h.byte(0) & 0x0fu, ttl = h.byte(8);
-    const bool dgram = ipv4 && len >= 34 && ver == 4 && hlen >= 5 && fold_value(ipv4_header_sum(h)) == h.be16(10);
+    const bool dgram = ipv4 && len >= 34 && hdr_parses(h);
     uint32_t st = (for_us ? kFrForUs : 0u) | (ipv4 ? kFrIpv4 : 0u) | (arp ? kFrArp : 0u) | (arp_ok ? kFrArpOk : 0u) |
                   (dgram ? kFrDgram : 0u);
     if constexpr (!kHop) {
       if (valid) status[i] = uint8_t(st);
     } else {
-      // Router::route: ttl <= 1 dropped, else ttl-- and compute_checksum()
-      const bool fwd = dgram && ttl > 1;
-      h.w[2] = (h.w[2] & ~0xffu) | ((ttl - 1) & 0xffu);
-      const uint32_t c = fold_value(ipv4_header_sum(h));
+      // Router::route: ttl <= 1 dropped
+      const bool fwd = dgram && h.byte(8) > 1;
+      uint32_t o[5];
+      hop_rewrite(h, o);
       uint32_t r_if = kNoRoute, r_hop = 0u, e0 = 0u, e1 = 0u, e2 = 0u, e3 = 0u;
-      const bool routed = fwd && route_find(rt, __builtin_bswap32(h.w[4]), r_if, r_hop);
+      const bool routed = fwd && route_find(rt, bswap32(o[4]), r_if, r_hop);
       st |= fwd ? (routed ? 3u : 1u) : 0u;
       if (routed) {
         // send_datagram on the egress interface: its own cache, its own address
@@ -208,21 +163,9 @@ __global__ __launch_bounds__(kBlock) void k_frame(const uint8_t* __restrict__ fr
       rec[1] = e1;
       rec[2] = e2;
       rec[3] = e3;
-      rec[4] = fwd ? h.w[0] : 0u;
-      rec[5] = fwd ? h.w[1] & ~0x00800000u : 0u;  // the flags word re-serialized: reserved bit dropped
-      rec[6] = fwd ? (h.w[2] & 0x0000ffffu) | ((c >> 8) << 16) | ((c & 0xffu) << 24) : 0u;
-      rec[7] = fwd ? h.w[3] : 0u;
-      rec[8] = fwd ? h.w[4] : 0u;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      // the wave's frames [wbase, wbase + 64): 576 consecutive dwords of the array
-      const uint64_t cnt = wbase < n ? (n - wbase < kPerWave ? n - wbase : kPerWave) : 0;
 #pragma unroll
-      for (uint32_t j = 0; j < kRec; ++j) {
-        const uint32_t t = j * 64u + lane64;
-        if (t < cnt * kRec) hdr_out[wbase * kRec + t] = sw[t];
-      }
+      for (int k = 0; k < 5; ++k) rec[4 + k] = fwd ? o[k] : 0u;
+      wave_store<kRec>(sw, hdr_out, wbase, n, lane64);
     }
     __builtin_amdgcn_wave_barrier();  // the next pass rewrites the wave's LDS
   }

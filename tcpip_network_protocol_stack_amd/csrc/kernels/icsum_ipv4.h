@@ -15,6 +15,7 @@ struct Hdr {
   __device__ __forceinline__ uint32_t byte(int k) const { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
   __device__ __forceinline__ uint32_t be16(int k) const { return (byte(k) << 8) | byte(k + 1); }
 };
+constexpr uint32_t kIpv4ReservedFlag = 0x00800000u;  // wire byte 6 bit 7, in w[1]: serialize() never writes it
 
 // The aligned dword holding the byte before `end`: the last dword a load for
 // a range ending at `end` (exclusive) may touch.
@@ -174,7 +175,7 @@ __device__ __forceinline__ void group_hdr_take(const GroupHdr& g, Hdr& h, uint32
 __device__ __forceinline__ uint32_t ipv4_header_sum(const Hdr& h) {
   uint32_t e = 0, o = 0;
   acc_dword(h.w[0], e, o);
-  acc_dword(h.w[1] & ~0x00800000u, e, o);
+  acc_dword(h.w[1] & ~kIpv4ReservedFlag, e, o);
   acc_dword(h.w[2] & 0x0000ffffu, e, o);
   acc_dword(h.w[3], e, o);
   acc_dword(h.w[4], e, o);

@@ -25,6 +25,8 @@
 //   icsum_wrap.h        k_tcp_wrap, k_tcp_hdr
 //   icsum_tick.h        k_tick, k_tick_server
 //   icsum_route.h       the route image walk (Router::match), k_route_lookup
+//   icsum_hdrpass.h     what the header-only passes share: rows_load / row_take, pair_hdr_load,
+//                       hdr_parses / hop_rewrite, wave_store (no kernels; router, frame, unwrap include it)
 //   icsum_router.h      k_router_ttl, k_router_hdrs (<true>: the route lookup fused)
 //   icsum_frame.h       k_frame (<false>: recv_frame's classification, <true>: the hop over Ethernet frames)
 //   icsum_unwrap.h      k_tcp_unwrap (message records behind the VERIFY launch)

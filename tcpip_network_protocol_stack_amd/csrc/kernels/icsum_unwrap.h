@@ -7,29 +7,18 @@
 // status bytes.  The host restatement is csrc/icsum_unwrap.cpp.
 #pragma once
 
-#include "icsum_ipv4.h"
+#include "icsum_hdrpass.h"
 
 namespace icsum {
 namespace {
 
-// A header-only pass in k_frame's shape (icsum_frame.h): a wave takes 64
-// consecutive datagrams per pass, in two phases.
-// Load: speculating hlen 5, a datagram's bytes 0..35 (the IPv4 header, then TCP
-// bytes 0..15) lie in at most four of the aligned 16-byte blocks that hold it.
-// Four lanes per datagram, lane j loading block j with ONE dwordx4 load
-// clamped at the datagram's last block (a datagram below 20 bytes, or one past
-// the batch, reads the zero pad): four load instructions per 64 datagrams, and
-// nothing outside the blocks that hold the datagram is read.  The blocks go to
-// LDS, one 17-dword row per datagram (the odd length keeps 64 rows on
-// different banks).
-// Parse: ONE lane per datagram.  It reads the ten dwords from the datagram's
-// start dword on, aligns them (alignbyte by the start's low two bits), reads
-// its status byte and builds the record.  A datagram with IPv4 options (rare)
-// loads its TCP dwords at 4 * hlen itself, the fifth clamped to the
-// datagram's last dword, as load_tcp_fields does.  Decisions read only bytes
-// the length check has shown to exist — `parsed` below holds only when
-// 4 * hlen + 20 <= length, whatever the status byte says — so clamped blocks
-// are never interpreted.
+// A header-only pass in rows (rows_load / row_take, icsum_hdrpass.h): a wave
+// takes 64 consecutive datagrams per pass.  Speculating hlen 5, the row holds
+// the IPv4 header and TCP bytes 0..15; the parsing lane reads its status byte
+// and builds the record.  A datagram with IPv4 options (rare) loads its TCP
+// dwords at 4 * hlen itself, the fifth clamped to the datagram's last dword,
+// as load_tcp_fields does.  `parsed` below holds only when 4 * hlen + 20 <=
+// length, whatever the status byte says.
 // Store: the wave stages its 64 records in the LDS rows it has just read (ten
 // dwords each) and stores them as 640 consecutive dwords.
 __global__ __launch_bounds__(kBlock) void k_tcp_unwrap(const uint8_t* __restrict__ dg,
@@ -38,59 +27,26 @@ __global__ __launch_bounds__(kBlock) void k_tcp_unwrap(const uint8_t* __restrict
                                                        const uint8_t* __restrict__ status,
                                                        uint32_t* __restrict__ recs,
                                                        const uint32_t* __restrict__ zpad) {
-  constexpr uint32_t kPerWave = 64, kRec = 10, kRow = 17;
-  __shared__ uint32_t raw[kBlock / 64][kPerWave * kRow];
+  constexpr uint32_t kRec = 10;
+  __shared__ uint32_t raw[kBlock / 64][kRowsPerWave * kRow];
   const uint32_t lane64 = threadIdx.x & 63u;
   uint32_t* const rw = raw[threadIdx.x >> 6];
   const uint64_t step = uint64_t(gridDim.x) * kBlock;
   const uint32_t bsh = frame_shift(dg);
-  dg -= bsh;  // 16-byte aligned: block bounds are multiples of 16 in this frame
+  dg -= bsh;
   for (uint64_t g0 = uint64_t(blockIdx.x) * kBlock; g0 < n; g0 += step) {  // uniform per block
-    const uint64_t wbase = g0 + (threadIdx.x >> 6) * kPerWave;
-    // ---- load: pass q brings datagrams wbase + 16 q .. + 15, four lanes each
-    u32x4 v[4];
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      const uint64_t j = wbase + 16u * q + (lane64 >> 2);
-      uint64_t s, e;
-      seg_bounds(offsets, stride, dlen, j < n ? j : n - 1, s, e, bsh);
-      const bool hdr = j < n && e >= s && e - s >= 20;
-      const uint32_t blk = lane64 & 3u;
-      const uint64_t a0 = s & ~uint64_t(15), alast = (e - 1) & ~uint64_t(15);
-      const uint64_t at = a0 + 16u * blk < alast ? a0 + 16u * blk : alast;
-      const u32x4* src = hdr ? reinterpret_cast<const u32x4*>(dg + at) : reinterpret_cast<const u32x4*>(zpad) + blk;
-#ifdef ICSUM_BOUNDS_CHECK
-      if (hdr) ICS_CHECK16(src, dg + a0, dg + ((e + 15) & ~uint64_t(15)));
-#endif
-      v[q] = *src;
-    }
-#pragma unroll
-    for (uint32_t q = 0; q < 4; ++q) {
-      uint32_t* row = rw + (16u * q + (lane64 >> 2)) * kRow + 4u * (lane64 & 3u);
-      row[0] = v[q].x;
-      row[1] = v[q].y;
-      row[2] = v[q].z;
-      row[3] = v[q].w;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const uint64_t wbase = g0 + (threadIdx.x >> 6) * kRowsPerWave;
+    rows_load<20>(dg, offsets, stride, dlen, n, bsh, wbase, lane64, zpad, rw);
     // ---- parse: lane l has datagram wbase + l
     const uint64_t i = wbase + lane64;
     const bool valid = i < n;
     uint64_t s, e;
     seg_bounds(offsets, stride, dlen, valid ? i : n - 1, s, e, bsh);
-    const uint64_t len = e >= s ? e - s : 0;
+    const uint64_t len = item_len(s, e);
     const bool hdr = valid && len >= 20;
     const uint32_t st = valid ? status[i] : 0u;
-    const uint32_t o = hdr ? uint32_t(s & 15u) >> 2 : 0u, sh = hdr ? uint32_t(s & 3u) : 0u;
-    uint32_t d[10];
-#pragma unroll
-    for (int w = 0; w < 10; ++w) d[w] = rw[lane64 * kRow + o + w];  // o + 9 <= 12
-    // f[k]: datagram bytes 4k .. 4k + 3; f[5..8] are TCP bytes 0..15 when hlen is 5
-    uint32_t f[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) f[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh);
+    uint32_t f[9];  // f[5..8] are TCP bytes 0..15 when hlen is 5
+    row_take(rw, lane64, hdr, s, f);
     const uint32_t hlen = f[0] & 0x0fu, hl = 4u * hlen;
     // PARSED (include/icsum.h), and the bytes it promises are there: the header
     // and 20 bytes of TCP behind it
@@ -115,10 +71,7 @@ __global__ __launch_bounds__(kBlock) void k_tcp_unwrap(const uint8_t* __restrict
     const uint32_t doff = (t3 & 0xffu) >> 4, flags = (t3 >> 8) & 0x17u;
     const uint64_t po64 = uint64_t(hl) + 4u * doff;
     const uint32_t pay_off = uint32_t(po64 < len ? po64 : len);
-    // every lane has read its row: the rows become the staging area
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();  // every lane has read its row: the rows become the staging area
     uint32_t* rec = rw + lane64 * kRec;
     rec[0] = parsed ? bswap32(f[3]) : 0u;                                        // src
     rec[1] = parsed ? bswap32(f[4]) : 0u;                                        // dst
@@ -130,16 +83,7 @@ __global__ __launch_bounds__(kBlock) void k_tcp_unwrap(const uint8_t* __restrict
     rec[7] = parsed ? pay_off : 0u;
     rec[8] = parsed ? uint32_t(len - pay_off) : 0u;
     rec[9] = st;  // status, reserved[3]
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // the wave's datagrams [wbase, wbase + 64): 640 consecutive dwords of the array
-    const uint64_t cnt = wbase < n ? (n - wbase < kPerWave ? n - wbase : kPerWave) : 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kRec; ++j) {
-      const uint32_t t = j * 64u + lane64;
-      if (t < cnt * kRec) recs[wbase * kRec + t] = rw[t];
-    }
+    wave_store<kRec>(rw, recs, wbase, n, lane64);
     __builtin_amdgcn_wave_barrier();  // the next pass rewrites the wave's LDS
   }
 }
