@@ -497,6 +497,143 @@ int ics_tcp_unwrap_batch(ics_ctx* ctx, const void* d_dgrams, const uint64_t* d_o
 int ics_tcp_unwrap_batch_host(ics_ctx* ctx, const void* h_dgrams, const uint64_t* h_offsets, uint64_t stride,
                               uint64_t dgram_len, uint64_t n, ics_tcp_rx* h_recs);
 
+/* ---- receive streams: TCPReceiver + Reassembler per batch ----------------- */
+/* The in-order byte stream of one connection, kept in a ring in device memory:
+ * what TCPReceiver::receive (src/tcp_receiver/tcp_receiver.cpp:4-44) ->
+ * Reassembler::insert (src/reassembler/reassembler.cpp:4-103) -> Writer::push
+ * (src/byte_stream/byte_stream.cpp:60-67) do with the payloads of a batch of
+ * ics_tcp_rx records, without a payload byte crossing to the host.
+ *   Control plane (host, sequential, exact; needs no context and no GPU): an
+ * ics_rx_stream holds the reference's state without the bytes — capacity C, the
+ * optional ISN, bytes_pushed (== first_unassembled_index_), bytes_popped,
+ * eof_index (UINT64_MAX until a FIN sets it), the closed and error flags and
+ * the ordered interval list, each interval with the list of source ranges its
+ * bytes come from in place of interval_str.  receive of one record performs the
+ * reference's statements in their order; what follows from that is reproduced
+ * bit for bit:
+ *   - an RST sets the error and returns; a set error makes every later receive
+ *     return at once;
+ *   - before the ISN is set a record without SYN is dropped; the first SYN's
+ *     seqno becomes the ISN;
+ *   - a SYN always inserts at stream index 0, whatever its seqno (a second SYN
+ *     with another seqno too);
+ *   - absseq = unwrap(seqno, isn, bytes_pushed + 1) with the reference's
+ *     conversions (the raw difference as an int32_t, the sum as an int64_t,
+ *     + 2^32 when negative); stream index absseq - 1, which for absseq == 0 (the
+ *     ISN itself without SYN) is UINT64_MAX and is rejected by `>= eof_index`;
+ *   - insert rejects on a closed stream, first >= eof_index, or first >=
+ *     first_unassembled + available_capacity;
+ *   - a FIN that passes those tests sets eof_index = first + length even when
+ *     its range, clipped to [first_unassembled, first_unassembled + available),
+ *     is empty (a FIN behind the window is rejected and sets nothing);
+ *   - merging, against the interval before (`prev`) and those behind:
+ *       touching intervals merge (prev.end >= new.beg);
+ *       a new range wholly inside prev (prev.end > new.end) is discarded;
+ *       otherwise the new range WINS its overlap with prev;
+ *       a following interval that ends later KEEPS its overlap;
+ *       a covered following interval is erased;
+ *     where overlapping segments carry different bytes these rules decide byte
+ *     by byte which source survives — there is no "overlaps must agree" contract;
+ *   - intervals are pushed while their start equals first_unassembled, and the
+ *     stream closes when first_unassembled >= eof_index.
+ * The one deliberate difference: capacity must be 1 .. 2^30 (ICS_ERR_INVALID
+ * otherwise): the ring is a device allocation.  Reader::pop beyond
+ * bytes_buffered (undefined in the reference) is refused.
+ *   Data plane: a batch's plan ends in a copy list; stream byte i lives at ring
+ * offset i mod C, pending bytes included (they lie inside [popped, popped + C)). */
+typedef struct ics_rx_stream ics_rx_stream;
+typedef struct ics_copy_piece { /* 16 bytes */
+  uint64_t src;               /* byte offset in the source (datagram) buffer */
+  uint32_t dst;               /* byte offset in the destination (ring): stream index mod C */
+  uint32_t len;               /* bytes; may be 0 */
+} ics_copy_piece;
+typedef struct ics_rx_send_t { /* TCPReceiver::send (tcp_receiver.cpp:47-67) */
+  uint32_t has_ackno;         /* the ISN is set */
+  uint32_t ackno;             /* wrap(bytes_pushed + 1 + closed, isn), raw; 0 without has_ackno */
+  uint16_t window;            /* min(available_capacity, 65535) */
+  uint8_t rst;                /* the stream's error flag */
+  uint8_t reserved;
+} ics_rx_send_t;
+typedef struct ics_rx_stats_t {
+  uint64_t capacity, bytes_pushed, bytes_popped, bytes_buffered;
+  uint64_t bytes_pending;     /* Reassembler::bytes_pending */
+  uint64_t available_capacity;
+  uint64_t eof_index;         /* UINT64_MAX: none yet */
+  uint64_t intervals;         /* pending intervals */
+  uint32_t closed, error;
+  uint32_t finished;          /* closed and nothing buffered (Reader::is_finished) */
+  uint32_t has_isn;
+} ics_rx_stats_t;
+/* A stream object without a ring (the CPU-only path: ics_rx_stream_plan and the
+ * queries below; the device calls refuse it). */
+int ics_rx_stream_create_host(uint64_t capacity, ics_rx_stream** out);
+/* ... and with its ring of `capacity` bytes on ctx's device.  Such a stream
+ * refers to its context: destroy it BEFORE ics_destroy(ctx). */
+int ics_rx_stream_create(ics_ctx* ctx, uint64_t capacity, ics_rx_stream** out);
+int ics_rx_stream_destroy(ics_rx_stream* rxs);
+/* receive over records 0 .. n-1 in order: take[i] != 0 selects record i; take
+ * == NULL selects every record with (status & 7) == 7 and ICS_ST_PROTO_TCP.
+ * Datagram i starts at h_offsets[i] (n + 1 host offsets) or at i * stride with
+ * dgram_len bytes.  After the last record the batch's copy list is written:
+ * every byte now held, pending or pushed, whose surviving source is a record of
+ * this batch lies in exactly one piece, src = the datagram's start + pay_off +
+ * the clip, dst = stream index mod C.  Pieces come in increasing stream index,
+ * are split at the ring's wrap and maximal otherwise, and have pairwise
+ * disjoint destinations; bytes an earlier batch left in the ring and that still
+ * win are not copied again.  *m = the number of pieces.  pieces == NULL: a dry
+ * run that only counts (the state is left as it was).  ICS_ERR_INVALID, with the
+ * state and the outputs untouched: cap < *m would be needed, a taken record
+ * whose pay_off + pay_len exceeds its datagram, decreasing offsets. */
+int ics_rx_stream_plan(ics_rx_stream* rxs, const ics_tcp_rx* recs, uint64_t n, const uint8_t* take,
+                       const uint64_t* h_offsets, uint64_t stride, uint64_t dgram_len, ics_copy_piece* pieces,
+                       uint64_t cap, uint64_t* m);
+int ics_rx_stream_send(ics_rx_stream* rxs, ics_rx_send_t* out);
+int ics_rx_stream_stats(ics_rx_stream* rxs, ics_rx_stats_t* out);
+/* Reader::pop; refused (ICS_ERR_INVALID) beyond bytes_buffered. */
+int ics_rx_stream_pop(ics_rx_stream* rxs, uint64_t len);
+/* The ring ranges that hold stream bytes [popped, pushed): *ranges = 0, 1 or 2,
+ * range k = ring bytes [off[k], off[k] + len[k]), in stream order. */
+int ics_rx_stream_peek(ics_rx_stream* rxs, uint32_t off[2], uint32_t len[2], uint32_t* ranges);
+/* reader().set_error() */
+int ics_rx_stream_set_error(ics_rx_stream* rxs);
+
+/* The copy kernel on its own (k_copy_pieces): for each of m pieces in device
+ * memory, d_dst[dst .. dst + len) = d_src[src .. src + len).  Contract:
+ * destinations pairwise disjoint; the two buffers do not overlap; every piece
+ * inside src_bytes / dst_bytes; len may be 0; neither src nor dst (nor the
+ * two bases) needs any alignment; dst_bytes <= 2^31.  Loads stay inside the
+ * aligned 16-byte blocks that hold a piece's source bytes; a destination block
+ * shared with a neighbouring piece is written with stores that cover only this
+ * piece's bytes (never read, merged and written back).  m == 0 launches
+ * nothing.  libicsum_debug.so checks every load against the piece's envelope
+ * and the source buffer and every store against [0, dst_bytes). */
+int ics_copy_pieces(ics_ctx* ctx, const void* d_src, uint64_t src_bytes, void* d_dst, uint64_t dst_bytes,
+                    const ics_copy_piece* d_pieces, uint64_t m, void* stream);
+
+/* The ring's device pointer (capacity bytes). */
+int ics_rx_stream_ring(ics_rx_stream* rxs, void** d_ring);
+/* One batch on the device: plans as ics_rx_stream_plan (the records, take and
+ * the offsets are HOST arrays — the offsets the caller uploaded for
+ * ics_tcp_unwrap_batch; d_dgrams is that call's device buffer), puts the copy
+ * list where the device reads it and launches k_copy_pieces on `stream`;
+ * nothing is launched when the list is empty.  The host state (send, stats,
+ * peek) is final on return; the bytes are in the ring once `stream` reaches the
+ * launch.  The copy list travels through a leased page-locked area that only
+ * grows, its event recorded behind the launch: no allocation and no
+ * synchronisation in the steady state.  Ordering is the caller's: calls on one
+ * ics_rx_stream go on one stream, or are synchronised between streams.
+ * The call plans on a copy of the state and commits it once the copy is
+ * enqueued: after ANY error (argument, ICS_ERR_NOMEM, ICS_ERR_HIP) the stream
+ * is as it was.  ICS_ERR_INVALID: a null context, stream or
+ * (n > 0) records, a stream without a ring or of another context, and what
+ * ics_rx_stream_plan refuses. */
+int ics_rx_stream_receive_batch(ics_ctx* ctx, ics_rx_stream* rxs, const void* d_dgrams, const uint64_t* h_offsets,
+                                uint64_t stride, uint64_t dgram_len, uint64_t n, const ics_tcp_rx* h_recs,
+                                const uint8_t* h_take, void* stream);
+/* read(): up to len buffered bytes to h_dst — peek, one or two copies on
+ * `stream`, synchronise, pop.  *got = the bytes read. */
+int ics_rx_stream_read(ics_ctx* ctx, ics_rx_stream* rxs, void* h_dst, uint64_t len, uint64_t* got, void* stream);
+
 /* ---- several batches in one launch -------------------------------------- */
 /* The receive and transmit paths hand the engine a stream of small batches —
  * one per event-loop tick or per filled arena (the reference reads its TUN fd
@@ -609,6 +746,7 @@ int ics_stream_synchronize(ics_ctx* ctx, void* stream);
 #define ICS_K_FRAME_RECV 20      /* k_frame<false>: recv_frame's classification (0 / 0) */
 #define ICS_K_ROUTER_FRAMES 21   /* k_frame<true>: the whole hop over Ethernet frames (0 / 0) */
 #define ICS_K_UNWRAP 22          /* k_tcp_unwrap behind the VERIFY launch: ics_tcp_unwrap_batch(_host) (0 / 0) */
+#define ICS_K_COPY_PIECES 23     /* k_copy_pieces: ics_copy_pieces, ics_rx_stream_receive_batch (0 / 0) */
 /* last_lps / last_unroll by kernel:
  *   ICS_K_CHECKSUM .. ICS_K_WRAP_2PASS  lanes per segment / loads in flight per lane
  *   ICS_K_TWOCLASS, ICS_K_IPV4_TWOCLASS  long-segment lanes (16) / segments per wave (16 or 32; 8 only under ICSUM_FORCE twoclass=8)

@@ -6,13 +6,13 @@ package is the binding used by tests/ and bench.py.
 """
 from ._lib import LIB_PATH, IcsumError, load  # noqa: F401
 
-__all__ = ["LIB_PATH", "IcsumError", "load", "Engine", "RouteTable", "NeighTable"]
+__all__ = ["LIB_PATH", "IcsumError", "load", "Engine", "RouteTable", "NeighTable", "RxStream"]
 
 
 def __getattr__(name):
     # torch is imported lazily so that `import tcpip_network_protocol_stack_amd`
     # stays cheap for the C-ABI-only users (symbol checks, FFI stubs)
-    if name in ("Engine", "RouteTable", "NeighTable", "engine"):
+    if name in ("Engine", "RouteTable", "NeighTable", "RxStream", "engine"):
         from . import engine
 
         return engine if name == "engine" else getattr(engine, name)

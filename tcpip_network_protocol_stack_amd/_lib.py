@@ -43,6 +43,30 @@ class TcpRx(ctypes.Structure):
 assert ctypes.sizeof(TcpRx) == 40
 
 
+class CopyPiece(ctypes.Structure):
+    """struct ics_copy_piece (include/icsum.h), 16 bytes: one run of a receive
+    stream's copy list (k_copy_pieces)."""
+    _fields_ = [("src", ctypes.c_uint64), ("dst", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+assert ctypes.sizeof(CopyPiece) == 16
+
+
+class RxSend(ctypes.Structure):
+    """struct ics_rx_send_t (include/icsum.h): TCPReceiver::send."""
+    _fields_ = [("has_ackno", ctypes.c_uint32), ("ackno", ctypes.c_uint32), ("window", ctypes.c_uint16),
+                ("rst", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class RxStats(ctypes.Structure):
+    """struct ics_rx_stats_t (include/icsum.h)."""
+    _fields_ = [("capacity", ctypes.c_uint64), ("bytes_pushed", ctypes.c_uint64), ("bytes_popped", ctypes.c_uint64),
+                ("bytes_buffered", ctypes.c_uint64), ("bytes_pending", ctypes.c_uint64),
+                ("available_capacity", ctypes.c_uint64), ("eof_index", ctypes.c_uint64),
+                ("intervals", ctypes.c_uint64), ("closed", ctypes.c_uint32), ("error", ctypes.c_uint32),
+                ("finished", ctypes.c_uint32), ("has_isn", ctypes.c_uint32)]
+
+
 class DispatchInfo(ctypes.Structure):
     """struct ics_dispatch_info_t (include/icsum.h): the last call's launch and
     the plan cache's counters."""
@@ -83,7 +107,7 @@ class NeighStats(ctypes.Structure):
 KERNELS = {1: "checksum", 2: "small", 3: "tiny", 4: "dense", 5: "twoclass", 6: "binned", 7: "ipv4",
            8: "ipv4_twoclass", 9: "wrap", 10: "wrap_2pass", 11: "router", 12: "batchv", 13: "tile",
            14: "router_hdrs", 15: "tick", 16: "tick_server", 17: "route_lookup", 18: "router_route",
-           19: "router_route_hdrs", 20: "frame_recv", 21: "router_frames", 22: "unwrap"}
+           19: "router_route_hdrs", 20: "frame_recv", 21: "router_frames", 22: "unwrap", 23: "copy_pieces"}
 ICS_RT_FORWARD, ICS_RT_ROUTED = 0x01, 0x02
 ICS_NO_ROUTE = 0xFFFFFFFF
 ICS_FR_RESOLVED, ICS_FR_DGRAM, ICS_FR_FOR_US, ICS_FR_IPV4, ICS_FR_ARP, ICS_FR_ARP_OK = 0x04, 0x08, 0x10, 0x20, 0x40, 0x80
@@ -143,6 +167,19 @@ SIGNATURES = {
     "ics_tcp_unwrap_one": (_int, [_p, ctypes.c_size_t, ctypes.POINTER(TcpRx)]),
     "ics_tcp_unwrap_batch": (_int, [_p, _p, _p, _u64, _u64, _u64, _p, _p, _p]),
     "ics_tcp_unwrap_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _p]),
+    "ics_rx_stream_create_host": (_int, [_u64, ctypes.POINTER(_p)]),
+    "ics_rx_stream_create": (_int, [_p, _u64, ctypes.POINTER(_p)]),
+    "ics_rx_stream_destroy": (_int, [_p]),
+    "ics_rx_stream_plan": (_int, [_p, _p, _u64, _p, _p, _u64, _u64, _p, _u64, ctypes.POINTER(_u64)]),
+    "ics_rx_stream_send": (_int, [_p, ctypes.POINTER(RxSend)]),
+    "ics_rx_stream_stats": (_int, [_p, ctypes.POINTER(RxStats)]),
+    "ics_rx_stream_pop": (_int, [_p, _u64]),
+    "ics_rx_stream_peek": (_int, [_p, _pu32, _pu32, _pu32]),
+    "ics_rx_stream_set_error": (_int, [_p]),
+    "ics_copy_pieces": (_int, [_p, _p, _u64, _p, _u64, _p, _u64, _p]),
+    "ics_rx_stream_ring": (_int, [_p, ctypes.POINTER(_p)]),
+    "ics_rx_stream_receive_batch": (_int, [_p, _p, _p, _p, _u64, _u64, _u64, _p, _p, _p]),
+    "ics_rx_stream_read": (_int, [_p, _p, _p, _u64, ctypes.POINTER(_u64), _p]),
     "ics_checksum_batch_host": (_int,[_p, _p, _p, _u64, _u64, _p, _p, _u64]),
     "ics_ipv4_tcp_batch_host": (_int, [_p, _p, _p, _u64, _u64, _u64, _int, _p, _p, _p]),
     "ics_malloc": (_int, [_p, ctypes.POINTER(_p), ctypes.c_size_t]),

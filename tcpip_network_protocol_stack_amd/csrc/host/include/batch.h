@@ -11,6 +11,9 @@
 //                         payloads copied once, into the DMA arena)
 //   unwrap()/unwrap_raw() TCPOverIPv4Adapter::unwrap_tcp_in_ip per datagram tcp_over_ip.cpp:10-67
 //   unwrap_records()      the same from the device's ics_tcp_rx records (fields parsed on the GPU)
+//   receive_records()     unwrap_records' gates, then TCPReceiver::receive per accepted message
+//                         into an icsum::RxStream whose bytes stay in device memory
+//                         (tcp_receiver.cpp:4-44, reassembler.cpp:4-103, byte_stream.cpp:60-67)
 //
 // Results are bit-identical to the per-object calls.  All checksum arithmetic
 // runs on the GPU; a BatchEngine cannot be constructed without one (there is
@@ -42,6 +45,39 @@ class WorkerPool;  // par_for.h
 // configuration `cfg` (tcp_over_ip.cpp:71-80, tcp_segment.cpp:76-106): the
 // record the device-side wrap (ics_tcp_wrap_batch) serializes.
 ics_tcp_msg wrap_fields(const FdAdapterConfig& cfg, const TCPMessage& msg);
+
+class BatchEngine;
+
+// One connection's receive stream (ics_rx_stream, include/icsum.h): the state
+// of TCPReceiver + Reassembler + ByteStream's writer on the host, the bytes in
+// a ring on the engine's device.  RxStream(capacity) alone is the CPU-only
+// object (plan and the queries); with an engine it has its ring and refers to
+// the engine's context: destroy it before the BatchEngine.
+class RxStream
+{
+  public:
+    explicit RxStream(uint64_t capacity);
+    RxStream(BatchEngine& eng, uint64_t capacity);
+    ~RxStream();
+    RxStream(const RxStream&) = delete;
+    RxStream& operator=(const RxStream&) = delete;
+
+    ics_rx_stream* get() const { return rxs_; }
+    TCPReceiverMessage send() const;  // TCPReceiver::send
+    ics_rx_stats_t stats() const;
+    // ics_rx_stream_plan over host records (CPU-only path): the batch's copy list
+    std::vector<ics_copy_piece> plan(std::span<const ics_tcp_rx> recs, const uint8_t* take, const uint64_t* offsets,
+                                     uint64_t stride = 0, uint64_t dgram_len = 0);
+    // the ring ranges (offset, length) that hold the buffered bytes, in stream order
+    std::vector<std::pair<uint32_t, uint32_t>> peek() const;
+    void pop(uint64_t len);  // Reader::pop; throws beyond bytes_buffered
+    void set_error();        // reader().set_error()
+    std::string read(uint64_t len);  // read(reader, len, out) from the device ring (needs an engine)
+
+  private:
+    ics_rx_stream* rxs_ = nullptr;
+    ics_ctx* ctx_ = nullptr;
+};
 
 class BatchEngine
 {
@@ -81,6 +117,17 @@ class BatchEngine
     std::vector<std::optional<TCPMessage>> unwrap_records(TCPOverIPv4Adapter& adapter, const uint8_t* bytes,
                                                           const uint64_t* offsets, size_t n);
 
+    // Receive path with the bytes left on the device: the datagrams are in
+    // device memory (d_dgrams, packed by the n + 1 HOST offsets).  The message
+    // records are parsed there (ics_tcp_unwrap_batch), unwrap_records' gates run
+    // on the host from record fields in datagram order, and every accepted
+    // message is received into `rx` (ics_rx_stream_receive_batch): its state is
+    // final on return, its bytes follow on the engine's stream.  No payload
+    // string is ever built.  Returns the number of accepted datagrams; `take`
+    // (optional, n bytes) receives which.
+    size_t receive_records(TCPOverIPv4Adapter& adapter, RxStream& rx, const void* d_dgrams, const uint64_t* offsets,
+                           size_t n, uint8_t* take = nullptr);
+
     // the resident tick server (ics_set_tick_server): a per-tick loop's calls
     // of <= 16 x blocks datagrams without a kernel launch each; 0 turns it
     // off; blocks 1..8 (ics_set_tick_server_blocks, default 4)
@@ -92,6 +139,7 @@ class BatchEngine
     void host_free(void* p);
 
     int device() const { return device_; }
+    ics_ctx* context() const { return ctx_; }  // for the C-ABI calls this class does not wrap
 
   private:
     template <typename Msgs, typename Take>
@@ -106,6 +154,8 @@ class BatchEngine
     int device_ = 0;
     uint8_t* scratch_ = nullptr;
     size_t scratch_cap_ = 0;
+    void* d_rx_ = nullptr;  // receive_records: device room for the offsets and the records, grown on demand
+    size_t d_rx_cap_ = 0;
     std::unique_ptr<detail::WorkerPool> pool_{};  // ranges()' workers, started on first use
 };
 

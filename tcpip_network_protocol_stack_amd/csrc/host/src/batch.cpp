@@ -60,6 +60,7 @@ BatchEngine::BatchEngine(int device) : device_(device)
 BatchEngine::~BatchEngine()
 {
     if (scratch_) ics_host_free(ctx_, scratch_);
+    if (d_rx_) ics_free(ctx_, d_rx_);
     ics_destroy(ctx_);
 }
 
@@ -380,6 +381,34 @@ std::vector<std::optional<TCPMessage>> BatchEngine::unwrap_packed(TCPOverIPv4Ada
     return out;
 }
 
+namespace {
+
+// unwrap_tcp_in_ip's gates from one record's fields (tcp_over_ip.cpp:14-64):
+// the message without its payload, or nothing
+std::optional<TCPMessage> gate_record(TCPOverIPv4Adapter& adapter, const ics_tcp_rx& r)
+{
+    constexpr uint8_t kParsed = ICS_ST_IPV4_OK | ICS_ST_TCP_CKSUM_OK | ICS_ST_TCP_HDR_OK;
+    if ((r.status & kParsed) != kParsed) return {};
+    IPv4Header h;  // the three fields the gates read
+    h.src = r.msg.src;
+    h.dst = r.msg.dst;
+    h.proto = (r.status & ICS_ST_PROTO_TCP) ? IPv4Header::PROTO_TCP : uint8_t{0};  // any other value fails ip_gate
+    if (!detail::ip_gate(adapter, h)) return {};
+    TCPSegment seg;
+    seg.udinfo.src_port = r.msg.src_port;
+    seg.udinfo.dst_port = r.msg.dst_port;
+    TCPMessage& m = seg.message;
+    m.sender.seqno = Wrap32{r.msg.seqno};
+    m.sender.SYN = (r.msg.flags & ICS_TCP_SYN) != 0;
+    m.sender.FIN = (r.msg.flags & ICS_TCP_FIN) != 0;
+    m.sender.RST = m.receiver.RST = (r.msg.flags & ICS_TCP_RST) != 0;
+    if (r.msg.flags & ICS_TCP_ACK) m.receiver.ackno = Wrap32{r.msg.ackno};
+    m.receiver.window_size = r.msg.window;
+    return detail::tcp_gate(adapter, h, std::move(seg));
+}
+
+}  // namespace
+
 std::vector<std::optional<TCPMessage>> BatchEngine::unwrap_records(TCPOverIPv4Adapter& adapter, const uint8_t* bytes,
                                                                    const uint64_t* offsets, size_t n)
 {
@@ -390,29 +419,108 @@ std::vector<std::optional<TCPMessage>> BatchEngine::unwrap_records(TCPOverIPv4Ad
     if (n == 0) return out;
     std::vector<ics_tcp_rx> rec(n);
     check(ics_tcp_unwrap_batch_host(ctx_, bytes, offsets, 0, 0, n, rec.data()), "ics_tcp_unwrap_batch_host");
-    constexpr uint8_t kParsed = ICS_ST_IPV4_OK | ICS_ST_TCP_CKSUM_OK | ICS_ST_TCP_HDR_OK;
     for (size_t i = 0; i < n; ++i) {
         const ics_tcp_rx& r = rec[i];
-        if ((r.status & kParsed) != kParsed) continue;
-        IPv4Header h;  // the three fields the gates read
-        h.src = r.msg.src;
-        h.dst = r.msg.dst;
-        h.proto = (r.status & ICS_ST_PROTO_TCP) ? IPv4Header::PROTO_TCP : uint8_t{0};  // any other value fails ip_gate
-        if (!detail::ip_gate(adapter, h)) continue;
-        TCPSegment seg;
-        seg.udinfo.src_port = r.msg.src_port;
-        seg.udinfo.dst_port = r.msg.dst_port;
-        TCPMessage& m = seg.message;
-        m.sender.seqno = Wrap32{r.msg.seqno};
-        m.sender.SYN = (r.msg.flags & ICS_TCP_SYN) != 0;
-        m.sender.FIN = (r.msg.flags & ICS_TCP_FIN) != 0;
-        m.sender.RST = m.receiver.RST = (r.msg.flags & ICS_TCP_RST) != 0;
-        if (r.msg.flags & ICS_TCP_ACK) m.receiver.ackno = Wrap32{r.msg.ackno};
-        m.receiver.window_size = r.msg.window;
-        out[i] = detail::tcp_gate(adapter, h, std::move(seg));
+        out[i] = gate_record(adapter, r);
         if (out[i] && r.pay_len)
             out[i]->sender.payload.assign(reinterpret_cast<const char*>(bytes) + offsets[i] + r.pay_off, r.pay_len);
     }
+    return out;
+}
+
+size_t BatchEngine::receive_records(TCPOverIPv4Adapter& adapter, RxStream& rx, const void* d_dgrams,
+                                    const uint64_t* offsets, size_t n, uint8_t* take_out)
+{
+    if (n == 0) return 0;
+    // device room: the n + 1 offsets, then the n records (8-byte aligned)
+    const size_t off_bytes = (n + 1) * sizeof(uint64_t), need = off_bytes + n * sizeof(ics_tcp_rx);
+    if (need > d_rx_cap_) {
+        if (d_rx_) check(ics_free(ctx_, d_rx_), "ics_free");
+        d_rx_ = nullptr;
+        d_rx_cap_ = 0;
+        check(ics_malloc(ctx_, &d_rx_, need * 2), "ics_malloc");
+        d_rx_cap_ = need * 2;
+    }
+    auto* d_off = static_cast<uint64_t*>(d_rx_);
+    auto* d_rec = reinterpret_cast<ics_tcp_rx*>(static_cast<uint8_t*>(d_rx_) + off_bytes);
+    check(ics_memcpy_htod(ctx_, d_off, offsets, off_bytes, nullptr), "ics_memcpy_htod");
+    check(ics_tcp_unwrap_batch(ctx_, d_dgrams, d_off, 0, 0, n, d_rec, nullptr, nullptr), "ics_tcp_unwrap_batch");
+    std::vector<ics_tcp_rx> rec(n);
+    check(ics_memcpy_dtoh(ctx_, rec.data(), d_rec, n * sizeof(ics_tcp_rx), nullptr), "ics_memcpy_dtoh");
+    check(ics_stream_synchronize(ctx_, nullptr), "ics_stream_synchronize");
+    std::vector<uint8_t> take(n, 0);
+    size_t accepted = 0;
+    for (size_t i = 0; i < n; ++i) {  // the gates are sequential: a listening adapter connects on its first SYN
+        take[i] = gate_record(adapter, rec[i]).has_value();
+        accepted += take[i];
+    }
+    check(ics_rx_stream_receive_batch(ctx_, rx.get(), d_dgrams, offsets, 0, 0, n, rec.data(), take.data(), nullptr),
+          "ics_rx_stream_receive_batch");
+    if (take_out) std::memcpy(take_out, take.data(), n);
+    return accepted;
+}
+
+// ---- RxStream ---------------------------------------------------------------
+RxStream::RxStream(uint64_t capacity) { check(ics_rx_stream_create_host(capacity, &rxs_), "ics_rx_stream_create_host"); }
+
+RxStream::RxStream(BatchEngine& eng, uint64_t capacity) : ctx_(eng.context())
+{
+    check(ics_rx_stream_create(ctx_, capacity, &rxs_), "ics_rx_stream_create");
+}
+
+RxStream::~RxStream() { ics_rx_stream_destroy(rxs_); }
+
+TCPReceiverMessage RxStream::send() const
+{
+    ics_rx_send_t s{};
+    check(ics_rx_stream_send(rxs_, &s), "ics_rx_stream_send");
+    TCPReceiverMessage m;
+    if (s.has_ackno) m.ackno = Wrap32{s.ackno};
+    m.window_size = s.window;
+    m.RST = s.rst != 0;
+    return m;
+}
+
+ics_rx_stats_t RxStream::stats() const
+{
+    ics_rx_stats_t st{};
+    check(ics_rx_stream_stats(rxs_, &st), "ics_rx_stream_stats");
+    return st;
+}
+
+std::vector<ics_copy_piece> RxStream::plan(std::span<const ics_tcp_rx> recs, const uint8_t* take, const uint64_t* offsets,
+                                           uint64_t stride, uint64_t dgram_len)
+{
+    uint64_t m = 0;
+    check(ics_rx_stream_plan(rxs_, recs.data(), recs.size(), take, offsets, stride, dgram_len, nullptr, 0, &m),
+          "ics_rx_stream_plan");
+    std::vector<ics_copy_piece> pieces(m + 1);  // never a null array: that would only count
+    check(ics_rx_stream_plan(rxs_, recs.data(), recs.size(), take, offsets, stride, dgram_len, pieces.data(), m, &m),
+          "ics_rx_stream_plan");
+    pieces.resize(m);
+    return pieces;
+}
+
+std::vector<std::pair<uint32_t, uint32_t>> RxStream::peek() const
+{
+    uint32_t off[2], len[2], k = 0;
+    check(ics_rx_stream_peek(rxs_, off, len, &k), "ics_rx_stream_peek");
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    for (uint32_t i = 0; i < k; ++i) out.emplace_back(off[i], len[i]);
+    return out;
+}
+
+void RxStream::pop(uint64_t len) { check(ics_rx_stream_pop(rxs_, len), "ics_rx_stream_pop"); }
+
+void RxStream::set_error() { check(ics_rx_stream_set_error(rxs_), "ics_rx_stream_set_error"); }
+
+std::string RxStream::read(uint64_t len)
+{
+    const uint64_t have = stats().bytes_buffered;
+    std::string out(static_cast<size_t>(std::min(len, have)), '\0');
+    uint64_t got = 0;
+    check(ics_rx_stream_read(ctx_, rxs_, out.data(), out.size(), &got, nullptr), "ics_rx_stream_read");
+    out.resize(static_cast<size_t>(got));
     return out;
 }
 

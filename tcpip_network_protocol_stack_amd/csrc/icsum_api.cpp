@@ -52,13 +52,16 @@ int bounds_verdict(hipStream_t st, int rc) {
   ICS_HIP(icsum::bounds_take(st, &flags, &what));
   if (flags)
     return fail(ICS_ERR_INVALID,
-                "bounds check: %s%s%s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
+                "bounds check: %s%s%s%s%s%s%s (first: %s 0x%llx)", (flags & 1u) ? "load outside a segment's envelope " : "",
                 (flags & 2u) ? "offsets not monotone " : "", (flags & 4u) ? "header load past a datagram " : "",
                 (flags & 8u) ? "route image index outside the image " : "",
                 (flags & 16u) ? "neighbour image slot outside the table " : "",
-                (flags & 2u) && !(flags & 29u)   ? "segment"
-                : (flags & 8u) && !(flags & 23u)  ? "image word"
-                : (flags & 16u) && !(flags & 15u) ? "image slot"
+                (flags & 32u) ? "copy piece load outside its source " : "",
+                (flags & 64u) ? "copy piece store outside the ring " : "",
+                (flags & 2u) && !(flags & 125u)   ? "segment"
+                : (flags & 8u) && !(flags & 119u)  ? "image word"
+                : (flags & 16u) && !(flags & 111u) ? "image slot"
+                : (flags & 64u) && !(flags & 63u)  ? "ring offset"
                                                   : "address",
                 (unsigned long long)what);
   return ICS_OK;
@@ -145,6 +148,7 @@ int ics_destroy(ics_ctx* ctx) {
     if (ctx->plan_host) (void)hipHostFree(ctx->plan_host);
     ctx->scratch.release();
     ctx->unwrap_status.release();
+    ctx->rx_pieces.release();
   }
   delete ctx;
   return ICS_OK;
@@ -287,6 +291,18 @@ int ics_tcp_unwrap_batch_host(ics_ctx* ctx, const void* h_dgrams, const uint64_t
   if (reinterpret_cast<uintptr_t>(h_recs) & 3u) return fail(ICS_ERR_INVALID, "record array not 4-byte aligned");
   return host_pipeline(ctx, 3, const_cast<void*>(h_dgrams), h_offsets, stride, dgram_len, nullptr, n, 0, nullptr,
                        nullptr, reinterpret_cast<uint8_t*>(h_recs), nullptr);
+}
+
+int ics_copy_pieces(ics_ctx* ctx, const void* d_src, uint64_t src_bytes, void* d_dst, uint64_t dst_bytes,
+                    const ics_copy_piece* d_pieces, uint64_t m, void* stream) {
+  if (int rc = bind(ctx)) return rc;
+  if (m == 0) return ICS_OK;
+  if (!d_src || !d_dst || !d_pieces) return fail(ICS_ERR_INVALID, "null device buffer");
+  if (reinterpret_cast<uintptr_t>(d_pieces) & 7u) return fail(ICS_ERR_INVALID, "piece array not 8-byte aligned");
+  if (dst_bytes > (uint64_t(1) << 31))
+    return fail(ICS_ERR_INVALID, "destination of %llu bytes above 2^31", (unsigned long long)dst_bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return bounds_verdict(st, copy_pieces_device(ctx, d_src, src_bytes, d_dst, dst_bytes, d_pieces, m, st));
 }
 
 int ics_checksum_batchv(ics_ctx* ctx, const ics_seg_batch* batches, uint32_t k, void* stream) {

@@ -1,10 +1,11 @@
 // icsum_ctx.h — internal to libicsum.so: the engine context (struct ics_ctx,
-// opaque in include/icsum.h) and what the four translation units behind the
+// opaque in include/icsum.h) and what the five translation units behind the
 // C-ABI share:
 //   icsum_api.cpp       argument validation, device binding, error strings, the extern "C" entry points
 //   icsum_dispatch.cpp  device-buffer dispatch: geometry choice, the plan cache, binning, multi-batch grouping
 //   icsum_images.cpp    the route and neighbour images' device residency and the launches that read them
 //   icsum_host.cpp      the host-memory (PCIe-inclusive) pipeline and its staging slots
+//   icsum_rxdev.cpp     the receive streams' rings, their copy lists' way to the device, receive_batch / read
 // Not installed, not part of the ABI.
 #pragma once
 
@@ -62,6 +63,36 @@ struct ScratchArea {
     }
     if (ev) (void)hipEventDestroy(ev);
     ev = nullptr;
+  }
+};
+
+// The copy lists of ics_rx_stream_receive_batch on their way to the device:
+// kSlots slots taken in turn, each a page-locked host buffer the planner's
+// list is copied into and a device buffer it is DMA'd to on the call's stream
+// in front of k_copy_pieces.  A slot's event is recorded behind that launch;
+// the call that takes the slot again (kSlots calls later) waits for it on the
+// host, which in the steady state it has long passed.  Buffers only grow (a
+// grown slot is first waited for); they live until ics_destroy.
+struct PieceArea {
+  static constexpr int kSlots = 4;
+  struct Slot {
+    void* h = nullptr;
+    void* d = nullptr;
+    size_t cap = 0;  // bytes
+    hipEvent_t ev = nullptr;
+    bool used = false;
+  };
+  std::mutex mu;
+  Slot slot[kSlots];
+  int next = 0;
+  void release() {
+    for (Slot& s : slot) {
+      if (s.used) (void)hipEventSynchronize(s.ev);
+      if (s.h) (void)hipHostFree(s.h);
+      if (s.d) (void)hipFree(s.d);
+      if (s.ev) (void)hipEventDestroy(s.ev);
+      s = Slot{};
+    }
   }
 };
 
@@ -168,6 +199,8 @@ struct ics_ctx {
   // `scratch` for its re-plan while this lease is held; its event is created
   // on first use (unwrap_device).
   icsum::detail::ScratchArea unwrap_status;
+  // ics_rx_stream_receive_batch: the copy lists' way to the device
+  icsum::detail::PieceArea rx_pieces;
   std::mutex mu;
   // host path: nslots slots (2..kMaxSlots, ICSUM_HOST_SLOTS) of slot_bytes each
   // (ICSUM_HOST_SLOT_MB), each with pinned in/out staging, device buffers and a stream
@@ -370,6 +403,10 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
 // unwrap_tcp_in_ip's parse: ipv4_device in VERIFY mode (status to d_status, or
 // to ctx->unwrap_status when null), then k_tcp_unwrap's records to d_recs.
 int unwrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, ics_tcp_rx* d_recs, uint8_t* d_status, hipStream_t st);
+// k_copy_pieces over m pieces already in device memory (ics_copy_pieces; the
+// receive streams' launch, icsum_rxdev.cpp).
+int copy_pieces_device(ics_ctx* ctx, const void* d_src, uint64_t src_bytes, void* d_dst, uint64_t dst_bytes,
+                       const void* d_pieces, uint64_t m, hipStream_t st);
 // c2: the router's TTL decrement + header checksum recompute, in place
 // (d_hdrs null) or with the forwarded headers to d_hdrs (20 bytes each).
 int router_device(ics_ctx* ctx, const icsum::SegSpec& sp, uint32_t* d_hdrs, uint8_t* d_status, hipStream_t st);

@@ -485,6 +485,15 @@ int wrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, const ics_tcp_msg* d_msg
   return issue_wrap(ctx, sp, d_msgs, hdr_out, d_ip_ck, d_tcp_ck, payload_only, L, pr.req, st);
 }
 
+// k_copy_pieces over a piece list in device memory (ics_copy_pieces, ics_rx_stream_receive_batch).
+int copy_pieces_device(ics_ctx* ctx, const void* d_src, uint64_t src_bytes, void* d_dst, uint64_t dst_bytes,
+                       const void* d_pieces, uint64_t m, hipStream_t st) {
+  ICS_HIP(icsum::launch_copy_pieces(static_cast<const uint8_t*>(d_src), src_bytes, static_cast<uint8_t*>(d_dst),
+                                    uint32_t(dst_bytes), d_pieces, m, st));
+  report_launch(ctx, ICS_K_COPY_PIECES);
+  return ICS_OK;
+}
+
 // The VERIFY dispatch exactly as ics_ipv4_tcp_batch runs it (same plan cache
 // slot, same choice), then one more launch on the stream for the records.
 int unwrap_device(ics_ctx* ctx, const icsum::SegSpec& sp, ics_tcp_rx* d_recs, uint8_t* d_status, hipStream_t st) {

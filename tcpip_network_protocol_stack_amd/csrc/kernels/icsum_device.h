@@ -41,6 +41,9 @@ constexpr unsigned kBoundsLoad = 1u, kBoundsOffsets = 2u, kBoundsHeader = 4u;
 constexpr unsigned kBoundsRoute = 8u;  // a route image word or record index outside the image (addr: the word index)
 // a neighbour image slot index outside the table, or a probe sequence that met no empty slot (addr: the slot index)
 constexpr unsigned kBoundsNeigh = 16u;
+// k_copy_pieces: a source block outside the piece's envelope or the source buffer (addr: the address), a store
+// outside [0, ring size) (addr: the ring offset)
+constexpr unsigned kBoundsPieceLoad = 32u, kBoundsPieceStore = 64u;
 __device__ __forceinline__ void bounds_fail(unsigned bit, unsigned long long what) {
   if (atomicOr(&g_icsum_bounds.flags, bit) == 0u) atomicExch(&g_icsum_bounds.addr, what);
 }

@@ -31,6 +31,7 @@
 //   icsum_frame.h       k_frame (<false>: recv_frame's classification, <true>: the hop over Ethernet frames)
 //   icsum_unwrap.h      k_tcp_unwrap (message records behind the VERIFY launch)
 //   icsum_span.h        k_span (tile launches)
+//   icsum_scatter.h     k_copy_pieces (the receive streams' gather / scatter)
 //   icsum_generators.h  the workload generators
 // (icsum_device.h: arithmetic primitives; icsum_launch.h: the launchers' interface)
 #include "icsum_common.h"
@@ -45,6 +46,7 @@
 #include "icsum_frame.h"
 #include "icsum_unwrap.h"
 #include "icsum_span.h"
+#include "icsum_scatter.h"
 #include "icsum_generators.h"
 
 namespace icsum {

@@ -218,6 +218,14 @@ hipError_t launch_frames(const SegSpec& sp, const RouteImg& rt, const NeighImg& 
 // `status`.
 hipError_t launch_tcp_unwrap(const SegSpec& sp, const uint8_t* status, uint32_t* recs, hipStream_t st);
 
+// The receive streams' copy list (kernels/icsum_scatter.h): m ics_copy_piece
+// records in device memory, 8-byte aligned; piece p copies src[p.src ..
+// p.src + p.len) to dst[p.dst .. p.dst + p.len).  dst_bytes <= 2^31; m == 0
+// launches nothing.  src_bytes / dst_bytes are read by the bounds-checked
+// build only.
+hipError_t launch_copy_pieces(const uint8_t* src, uint64_t src_bytes, uint8_t* dst, uint32_t dst_bytes,
+                              const void* pieces, uint64_t m, hipStream_t st);
+
 // Tile launches of offsets batches (k_span): one wave per S (1..63)
 // consecutive segments, the span's bytes streamed whole in 4 KiB windows
 // whatever the lengths.  Checksum (out_kind as launch_checksum), the fused IPv4/TCP kernel

@@ -9,6 +9,7 @@ the HIP kernels behind the C-ABI.  There is no fallback: a missing library or
 GPU raises.
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -29,6 +30,9 @@ assert TCP_MSG_DTYPE.itemsize == 28
 TCP_RX_DTYPE = np.dtype([("msg", TCP_MSG_DTYPE), ("pay_off", "<u4"), ("pay_len", "<u4"), ("status", "u1"),
                          ("reserved", "u1", (3,))])
 assert TCP_RX_DTYPE.itemsize == 40
+# struct ics_copy_piece (include/icsum.h) as a numpy record
+COPY_PIECE_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u4"), ("len", "<u4")])
+assert COPY_PIECE_DTYPE.itemsize == 16
 
 
 def _ptr(t):
@@ -177,6 +181,108 @@ class NeighTable:
             pass
 
 
+class RxStream:
+    """ics_rx_stream_*: one connection's receive stream — TCPReceiver +
+    Reassembler + the writer half of ByteStream on ics_tcp_rx records
+    (include/icsum.h has the rules).  RxStream(capacity) is the CPU-only
+    object (plan, send, stats, peek, pop: no Engine, no GPU);
+    Engine.rx_stream(capacity) adds the ring in device memory and receive /
+    read.  Records are TCP_RX_DTYPE arrays on the host."""
+
+    def __init__(self, capacity, engine=None, debug=False):
+        self.engine = engine
+        self.lib = engine.lib if engine is not None else _lib.load(_lib.DEBUG_LIB_PATH if debug else None)
+        h = ctypes.c_void_p()
+        if engine is not None:
+            check(self.lib.ics_rx_stream_create(engine.ctx, int(capacity), ctypes.byref(h)), self.lib)
+        else:
+            check(self.lib.ics_rx_stream_create_host(int(capacity), ctypes.byref(h)), self.lib)
+        self.handle = h
+        self.capacity = int(capacity)
+        if engine is not None:  # a stream with a ring must go before its context: Engine.close() closes it
+            engine._streams.add(self)
+
+    @staticmethod
+    def _batch(recs, take, offsets):
+        recs = np.ascontiguousarray(recs, dtype=TCP_RX_DTYPE)
+        take = None if take is None else np.ascontiguousarray(take, dtype=np.uint8)
+        offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+        return recs, take, offsets
+
+    def plan(self, recs, take=None, offsets=None, stride=0, dgram_len=0, dry=False):
+        """ics_rx_stream_plan over the records in order: the batch's copy list,
+        a COPY_PIECE_DTYPE array (src: byte offset in the datagram buffer, dst:
+        ring offset).  dry=True only counts (state unchanged) and returns m."""
+        recs, take, offsets = self._batch(recs, take, offsets)
+        m = ctypes.c_uint64()
+        args = (self.handle, _ptr(recs), len(recs), _ptr(take), _ptr(offsets), stride, dgram_len)
+        check(self.lib.ics_rx_stream_plan(*args, None, 0, ctypes.byref(m)), self.lib)
+        if dry:
+            return m.value
+        pieces = np.empty(m.value, dtype=COPY_PIECE_DTYPE)
+        check(self.lib.ics_rx_stream_plan(*args, pieces.ctypes.data, len(pieces), ctypes.byref(m)), self.lib)
+        return pieces[:m.value]
+
+    def receive(self, dgrams, recs, take=None, offsets=None, stride=0, dgram_len=0, stream=None):
+        """ics_rx_stream_receive_batch: `dgrams` the device tensor the records
+        were unwrapped from, `recs` / `take` / `offsets` host arrays.  The host
+        state is final on return; the bytes follow on `stream`."""
+        recs, take, offsets = self._batch(recs, take, offsets)
+        e = self.engine
+        check(self.lib.ics_rx_stream_receive_batch(e.ctx, self.handle, _ptr(dgrams), _ptr(offsets), stride, dgram_len,
+                                                   len(recs), _ptr(recs), _ptr(take), _stream(stream, e.device)),
+              self.lib)
+
+    def send(self):
+        """TCPReceiver::send: {'ackno' (None without an ISN), 'window', 'rst'}."""
+        o = _lib.RxSend()
+        check(self.lib.ics_rx_stream_send(self.handle, ctypes.byref(o)), self.lib)
+        return {"ackno": o.ackno if o.has_ackno else None, "window": o.window, "rst": bool(o.rst)}
+
+    def stats(self):
+        st = _lib.RxStats()
+        check(self.lib.ics_rx_stream_stats(self.handle, ctypes.byref(st)), self.lib)
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def peek(self):
+        """[(ring offset, length), ...]: the 0, 1 or 2 ring ranges holding [popped, pushed)."""
+        off, ln, k = (ctypes.c_uint32 * 2)(), (ctypes.c_uint32 * 2)(), ctypes.c_uint32()
+        check(self.lib.ics_rx_stream_peek(self.handle, off, ln, ctypes.byref(k)), self.lib)
+        return [(off[i], ln[i]) for i in range(k.value)]
+
+    def pop(self, n):
+        check(self.lib.ics_rx_stream_pop(self.handle, int(n)), self.lib)
+
+    def set_error(self):
+        check(self.lib.ics_rx_stream_set_error(self.handle), self.lib)
+
+    def ring(self):
+        """The ring's device address (ics_rx_stream_ring)."""
+        p = ctypes.c_void_p()
+        check(self.lib.ics_rx_stream_ring(self.handle, ctypes.byref(p)), self.lib)
+        return p.value
+
+    def read(self, n, stream=None):
+        """ics_rx_stream_read: up to n buffered bytes (popped) as `bytes`."""
+        buf = np.empty(max(int(n), 1), dtype=np.uint8)
+        got = ctypes.c_uint64()
+        e = self.engine
+        check(self.lib.ics_rx_stream_read(e.ctx, self.handle, buf.ctypes.data, int(n), ctypes.byref(got),
+                                          _stream(stream, e.device)), self.lib)
+        return buf[:got.value].tobytes()
+
+    def close(self):
+        if self.handle:
+            self.lib.ics_rx_stream_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One engine context bound to one GPU (ics_create / ics_destroy)."""
 
@@ -187,6 +293,7 @@ class Engine:
         ctx = ctypes.c_void_p()
         self._check(self.lib.ics_create(self.device.index or 0, ctypes.byref(ctx)))
         self.ctx = ctx
+        self._streams = weakref.WeakSet()  # rx_stream() objects, closed before the context
 
     def _check(self, rc):
         return check(rc, self.lib)
@@ -219,6 +326,8 @@ class Engine:
 
     def close(self):
         if self.ctx:
+            for rx in list(self._streams):
+                rx.close()
             self.lib.ics_destroy(self.ctx)
             self.ctx = None
 
@@ -353,6 +462,20 @@ class Engine:
         self._check(self.lib.ics_tcp_unwrap_batch(self.ctx, _ptr(dgrams), _ptr(offsets), stride, dgram_len, n,
                                                   _ptr(recs), _ptr(status), _stream(stream, self.device)))
         return recs
+
+    # ---- receive streams (TCPReceiver + Reassembler per batch) --------------
+    def rx_stream(self, capacity):
+        """ics_rx_stream_create: a receive stream with its ring on this GPU."""
+        return RxStream(capacity, engine=self)
+
+    def copy_pieces(self, src, dst, pieces, m=None, stream=None):
+        """ics_copy_pieces: dst[p.dst .. + p.len) = src[p.src .. + p.len) for
+        the m ics_copy_piece records of the device tensor `pieces` (uint8,
+        8-byte aligned); src / dst uint8 device tensors."""
+        m = pieces.numel() // 16 if m is None else int(m)
+        self._check(self.lib.ics_copy_pieces(self.ctx, _ptr(src), src.numel(), _ptr(dst), dst.numel(), _ptr(pieces),
+                                             m, _stream(stream, self.device)))
+        return dst
 
     def tcp_unwrap_batch_host(self, dgrams, n, offsets=None, stride=0, dgram_len=0, recs=None):
         """The same on host memory (numpy uint8 datagrams); returns a
